@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload x25519|mixed|sign|verify]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload x25519|mixed|sign|verify] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script re-launches itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU); launched by torchrun it reads
@@ -32,6 +32,8 @@ and `valu`: algorithmic 32x32 MACs against the measured v_mad_u64_u32 issue peak
 live on an un-profiled launch of the probe build (s_memtime inside the kernel) -- the SIMD cycles one ladder step costs
 against the issue model of its instruction stream (`issue_model_frac`) and the shader clock it ran at.
 cpu_baseline: the reference's portable-C path (oracle/_ref) or the oracle port on this host's cores.
+--dump-outputs DIR: behind all timed blocks, rank 0 writes the last timed step's outputs of every block (X25519 shared keys and
+clamped secret keys, signatures, verdicts) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import contextlib
@@ -97,6 +99,7 @@ WORKLOAD_NAME = {
 CLOCK_RAMP_S = 0.06      # untimed launches behind the opening barrier, directly in front of every block's timed steps (run_timed)
 DIGESTS = os.environ.get("C25519_BENCH_DIGESTS") or os.path.join(ROOT, "tests", "golden", "digests.json")   # (the env: tests only)
 DIGEST_KEY = {"x25519": "x25519_shared", "sign": "ed25519_sig", "verify": "ed25519_verdicts"}
+DUMP_NAME = {"x25519": "x25519_shared", "sign": "sign_signatures", "verify": "verify_verdicts"}      # --dump-outputs
 
 
 def expected_digests(rank, world, n):
@@ -440,6 +443,37 @@ def attest_ranks(identities, world, backend, share_gpu):
                                              and not any(a.get("compute_partition") for a in identities))}
 
 
+DUMP_SAMPLE_ROWS = 1 << 16      # --dump-outputs: rows kept of a larger output (a fixed, seeded sample; the same for every run)
+DUMP_SAMPLE_SEED = 0xD0D0
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: every output of the timed path's last step, as a caller of that path receives it, one
+    DIR/<name>.npy each (float32 for byte outputs, float64 for 32-bit words: exact either way).  An output of more than
+    DUMP_SAMPLE_ROWS rows keeps a seeded sample of its rows, in ascending order, and their indices go to DIR/<name>_rows.npy.
+    The inputs are seeded, so two builds run with the same arguments can be compared file for file.  Returns the file names."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    files, total = [], 0
+    for name, a in arrays:
+        a = np.asarray(a)
+        a = a.reshape(a.shape[0], -1)
+        todo = []
+        if a.shape[0] > DUMP_SAMPLE_ROWS:
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            a = a[rows]
+            todo.append((name + "_rows", rows.astype(np.float64)))
+        todo.append((name, a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)))
+        for fname, arr in todo:
+            total += arr.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+            np.save(os.path.join(dirname, fname + ".npy"), arr)
+            files.append(fname + ".npy")
+    return files
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -448,18 +482,45 @@ def free_port():
     return port
 
 
+def visible_gpu_count():
+    """torch.cuda.device_count() asked in a short-lived child: the launcher itself never opens the GPU, so the ranks it
+    starts are the only processes of this run that hold it."""
+    import subprocess
+    p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300)
+    try:
+        return int(p.stdout.strip().splitlines()[-1])
+    except (IndexError, ValueError):
+        sys.stderr.write(p.stderr[-2000:])
+        return 0
+
+
+def _die_with_parent():
+    """preexec_fn of the launcher's child: it gets SIGTERM when the launcher dies (a caller's time limit kills the launcher,
+    and torchrun then stops its ranks instead of running on as orphans)."""
+    import ctypes
+    import signal
+    try:
+        ctypes.CDLL(None, use_errno=True).prctl(1, int(signal.SIGTERM))     # PR_SET_PDEATHSIG
+    except Exception:
+        pass
+
+
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run ... bench.py ...`."""
-    import torch
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run ... bench.py ...` as a child
+    process and exit with its return code (stdout passes through: the ONE JSON line is rank 0's)."""
+    import subprocess
+    have = visible_gpu_count()
     if have < args.gpus and not (have and os.environ.get("C25519_BENCH_SHARE_GPU")):
         raise SystemExit(f"bench.py --gpus {args.gpus}: this machine exposes {have} GPU(s) to this process "
                          "(the launcher is fine; the devices are missing)")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd, env=env, preexec_fn=_die_with_parent).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -478,7 +539,12 @@ def main():
                          "sign); sign / verify = configs[2] / configs[3] alone; mixed = configs[4]")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="run the N>1 code path (process group + RCCL gather) with a world of one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of every timed block's last step as DIR/<name>.npy "
+                         "(rank 0's; float32 / float64, a seeded sample of 2^16 rows of larger outputs, 64 MB at most)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                              # does not return
@@ -746,6 +812,16 @@ def main():
             r["rejects_exactly_the_corrupted"] = bool((rejected == p["bad"]).all())
         return r
 
+    dumped = []                                            # --dump-outputs: (name, copy of a timed block's last output), rank 0
+
+    def keep(prefix, passes, run):
+        if not args.dump_outputs or rank != 0:
+            return
+        for j, p in enumerate(passes):
+            dumped.append((prefix + DUMP_NAME[p["wl"]], run["outs"][j].clone()))
+            if p["wl"] == "x25519":                        # the clamped secret keys are written back in place: an output too
+                dumped.append((prefix + "x25519_sk_clamped", p["sk"].clone()))
+
     wl = args.workload
     side = {}
     runs = []                                              # (name, pass, run) of every timed block, for the bit_exact summary
@@ -753,6 +829,7 @@ def main():
         (x0, x1), (s0, s1), (v0, v1) = mixed_thirds(n)
         passes = [make_x25519(x1 - x0, x0), make_sign(s1 - s0, s0), make_verify(v1 - v0, v0)]
         run = run_timed(passes, mixed=True)
+        keep("mixed_", passes, run)
         elapsed, kms = run["elapsed"], run["kms"]
         parts = [summarize(p, run, j) for j, p in enumerate(passes)]
         runs += [(p["wl"], r) for p, r in zip(passes, parts)]
@@ -781,12 +858,17 @@ def main():
     else:
         make = {"x25519": make_x25519, "sign": make_sign, "verify": make_verify}[wl]
         p = make(n)
-        primary = summarize(p, run_timed([p]))
+        run = run_timed([p])
+        keep("", [p], run)
+        primary = summarize(p, run)
         runs.append((wl, primary))
         if wl == "x25519" and not args.no_side:
             # the second half of BASELINE.json's metric, and config 3, with the same protocol
             for name, mk in (("verify", make_verify), ("sign", make_sign)):
-                side[name] = summarize(mk(n), run_timed([mk(n)]))
+                q = mk(n)
+                run = run_timed([q])
+                keep("", [q], run)
+                side[name] = summarize(q, run)
                 runs.append((name, side[name]))
 
     # ---- behind ALL timed blocks: the in-kernel probe.  Every rank measures the shader clock its X25519 ladder runs at
@@ -982,6 +1064,9 @@ def main():
     if use_dist:
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "rank": 0, "files": dump_outputs(
+                args.dump_outputs, [(name, t.cpu().numpy()) for name, t in dumped])}
         result["cpu_baseline"] = None if args.no_cpu else cpu_baseline(quick=world > 1)
         os.write(result_fd, (json.dumps(result) + "\n").encode())
         if result["bit_exact"]["mismatch"]:

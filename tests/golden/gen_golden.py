@@ -7,6 +7,7 @@ are data (inputs + the reference's outputs), never reference source.
     python tests/golden/gen_golden.py --no-big   # skip the 2^20 digests (minutes of CPU)
     python tests/golden/gen_golden.py --degenerate-only   # only degenerate_verify.npz (seconds)
     python tests/golden/gen_golden.py --ranks-only        # only digests.json["ranks"]: bench.py's ranks 0..7 at 2^20
+    python tests/golden/gen_golden.py --reference-diff-only   # only reference_diff.npz (seconds)
 
 Known-answer inputs come from RFC 7748 5.2, RFC 8032 7.1 and from the reference's own tests
 (test/curve25519_test.c:412-445, test/openssl_test.c:20,97,138); the expected outputs are whatever the
@@ -263,9 +264,21 @@ def degenerate(ref):
           + ", ".join(f"{c}: {int(verdict[label == c].sum())}/{int((label == c).sum())}" for c in sorted(set(label.tolist()))))
 
 
+def reference_diff(ref):
+    """reference_diff.npz: the reference's outputs on vectors.reference_differential's seeded inputs (the CPU suite's
+    test_against_reference_build compares the oracle with them)."""
+    import vectors
+    out = vectors.reference_differential(ref)
+    np.savez_compressed(os.path.join(HERE, "reference_diff.npz"), **out)
+    print(f"wrote reference_diff.npz: {len(out)} arrays")
+
+
 def main():
     assert Reference.available(), "build oracle/_ref first: make -C oracle ref"
     ref = Reference()
+    reference_diff(ref)
+    if "--reference-diff-only" in sys.argv:
+        return
     if "--ranks-only" in sys.argv:           # only digests.json["ranks"] (8 x 2^20 through the reference: ~10 min on 8 cores)
         path = os.path.join(HERE, "digests.json")
         with open(path) as f:

@@ -193,3 +193,36 @@ def test_the_committed_line_carries_the_mid_size_and_single_call_figures():
     assert mid["x25519"]["2^14"]["per_s"] > 4 * 9.6e6 and mid["sign"]["2^12"]["per_s"] > 2 * 22.8e6       # round 5: 2^12 X25519 9.6 M/s, 2^12 signatures 22.8 M/s
     assert one["bytes_equal_the_batch"] is True
     assert one["curve25519_dh_CreateSharedKey"] < 168 and one["ed25519_SignMessage"] < 105 and one["ed25519_VerifySignature"] < 135   # round 5's
+
+
+def test_dump_outputs_writes_exact_seeded_samples(tmp_path):
+    """--dump-outputs: one .npy per output, float32 for bytes and float64 for 32-bit words (exact), all rows of a small
+    output, a seeded sample of 2^16 rows (and their indices) of a large one -- the same rows in every run -- and 64 MB at most."""
+    import numpy as np
+    bench = load(os.path.join(ROOT, "bench.py"), "c25519_bench_dump")
+    rng = np.random.default_rng(7)
+    big = rng.integers(0, 256, (1 << 20, 64), dtype=np.uint8)
+    words = rng.integers(0, 2, (1 << 20, 1), dtype=np.int32)
+    small = rng.integers(0, 256, (1000, 32), dtype=np.uint8)
+    arrays = [("sign_signatures", big), ("verify_verdicts", words), ("x25519_shared", small)]
+    files = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(files) == sorted(["sign_signatures.npy", "sign_signatures_rows.npy", "verify_verdicts.npy",
+                                    "verify_verdicts_rows.npy", "x25519_shared.npy"])
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in files)
+    assert total <= 64 << 20
+    sig, rows = np.load(tmp_path / "a" / "sign_signatures.npy"), np.load(tmp_path / "a" / "sign_signatures_rows.npy")
+    assert sig.dtype == np.float32 and sig.shape == (1 << 16, 64) and rows.dtype == np.float64
+    assert np.all(np.diff(rows) > 0) and np.array_equal(sig, big[rows.astype(np.int64)].astype(np.float32))
+    ok = np.load(tmp_path / "a" / "verify_verdicts.npy")
+    assert ok.dtype == np.float64 and np.array_equal(ok, words[np.load(tmp_path / "a" / "verify_verdicts_rows.npy").astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "x25519_shared.npy"), small.astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "b"), arrays)                   # another run, the same inputs: the same files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+def test_bench_steps_must_be_positive():
+    import subprocess
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "--steps must be at least 1" in p.stderr, (bad, p.stderr[-1000:])

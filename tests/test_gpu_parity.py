@@ -24,7 +24,8 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 KAT = json.load(open(os.path.join(GOLD, "kat.json")))
 DIG = json.load(open(os.path.join(GOLD, "digests.json")))
 R1024 = np.load(os.path.join(GOLD, "random_1024.npz"))
-THREADS = os.cpu_count() or 1
+THREADS = min(os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 0) or 1 << 30)   # a share of a big host: its thread budget
+SHARED_GPU_MAX_PROCESSES = 6       # processes that may hold one device open at the same time (test_bench_self_launches_two_ranks)
 sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
 
 
@@ -1135,10 +1136,15 @@ def test_bench_self_launches_two_ranks(ranks, batch):
     N ranks share it (gloo gather, since RCCL refuses a duplicate device), so the self-launch under
     torch.distributed.run, the rank / seed / gather bookkeeping and the single JSON line from rank 0 are exercised
     for real -- with 2 ranks and with the 8 of the node the scaling bench runs on.  (The RCCL gather itself runs in
-    --dist-selftest with a world of one.)"""
+    --dist-selftest with a world of one.)  Every rank is a process that holds its device open, and a shared device takes
+    at most SHARED_GPU_MAX_PROCESSES of them, this test's own included: more ranks than that need more GPUs."""
     import torch
+    have = torch.cuda.device_count()
+    if have < ranks and 1 + ranks > SHARED_GPU_MAX_PROCESSES:
+        pytest.skip(f"needs {ranks} GPUs, found {have} ({ranks} ranks sharing them would be more than "
+                    f"{SHARED_GPU_MAX_PROCESSES} processes on one GPU)")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    if torch.cuda.device_count() < ranks:
+    if have < ranks:
         env["C25519_BENCH_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
                         "--batch", str(batch), "--no-cpu"], capture_output=True, text=True, timeout=240, env=env)
@@ -1156,6 +1162,57 @@ def test_bench_self_launches_two_ranks(ranks, batch):
     assert line["bit_exact"]["all"] is True
     assert all(r["bit_exact"] is True and r["ramp_launches"] >= 1 for r in line["per_rank"])
     assert len(line["per_rank_shader_clock_GHz"]) == ranks and all(1.0 < c < 3.0 for c in line["per_rank_shader_clock_GHz"])
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_computed(tmp_path, oracle):
+    """bench.py --dump-outputs DIR writes the last timed step's outputs: the mixed workload at 2^18 (thirds of more than 2^16
+    rows: seeded samples) and the default workload's X25519 block at 2^14 (every row), checked against the oracle on the
+    same seeded inputs; verdicts reject exactly the corrupted entries."""
+    def run(out, extra, n):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu",
+                            "--batch", str(n), "--dump-outputs", str(out)] + extra, capture_output=True, text=True, timeout=240)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads(p.stdout)
+        assert line["dump_outputs"]["dir"] == str(out) and line["bit_exact"]["mismatch"] is False
+        files = sorted(os.listdir(out))
+        assert sorted(line["dump_outputs"]["files"]) == files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        return files
+
+    def load(out, name, m):
+        a = np.load(out / (name + ".npy"))
+        rows = np.load(out / (name + "_rows.npy")).astype(np.int64) if os.path.exists(out / (name + "_rows.npy")) else np.arange(m)
+        assert a.shape[0] == rows.shape[0] and np.all(np.diff(rows) > 0) and rows[-1] < m
+        return a.astype(np.int64), rows
+
+    n = 1 << 18
+    files = run(tmp_path / "mixed", ["--workload", "mixed"], n)
+    assert files == sorted(f"mixed_{k}{r}.npy" for k in ("x25519_shared", "x25519_sk_clamped", "sign_signatures", "verify_verdicts")
+                           for r in ("", "_rows"))
+    out = tmp_path / "mixed"
+    (x0, x1), (s0, s1), (v0, v1) = synth.mixed_thirds(n)
+    sk, pk = synth.x25519_inputs(n)
+    got, rows = load(out, "mixed_x25519_shared", x1 - x0)
+    got_sk, rows_sk = load(out, "mixed_x25519_sk_clamped", x1 - x0)
+    assert np.array_equal(rows, rows_sk)
+    few = rows[:1024] + x0
+    exp, exp_sk = oracle.x25519_shared(pk[few], sk[few], threads=8)
+    assert np.array_equal(got[:1024], exp) and np.array_equal(got_sk[:1024], exp_sk)
+    esk, msg = synth.ed25519_inputs(n)
+    got, rows = load(out, "mixed_sign_signatures", s1 - s0)
+    few = rows[:1024] + s0
+    _, priv = oracle.ed25519_keypair(esk[few], threads=8)
+    assert np.array_equal(got[:1024], oracle.ed25519_sign(priv, msg[few], threads=8))
+    got, rows = load(out, "mixed_verify_verdicts", v1 - v0)
+    _, _, bad = synth.corrupt_for_verify(np.zeros((n, 64), np.uint8), np.zeros((n, 32), np.uint8))
+    assert np.array_equal(got.reshape(-1) == 0, bad[v0:v1][rows])
+
+    n = 1 << 14
+    assert run(tmp_path / "x", ["--no-side"], n) == sorted(["x25519_shared.npy", "x25519_sk_clamped.npy"])
+    sk, pk = synth.x25519_inputs(n)
+    exp, exp_sk = oracle.x25519_shared(pk, sk, threads=8)
+    assert np.array_equal(load(tmp_path / "x", "x25519_shared", n)[0], exp)
+    assert np.array_equal(load(tmp_path / "x", "x25519_sk_clamped", n)[0], exp_sk)
 
 
 def test_bench_detects_a_wrong_output_and_exits_nonzero():

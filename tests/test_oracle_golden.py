@@ -17,7 +17,7 @@ DIG = json.load(open(os.path.join(GOLD, "digests.json")))
 R1024 = np.load(os.path.join(GOLD, "random_1024.npz"))
 h2a = lambda s, w=None: np.frombuffer(bytes.fromhex(s), np.uint8).reshape(1, -1 if w is None else w)  # noqa: E731
 sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
-THREADS = os.cpu_count() or 1
+THREADS = min(os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 0) or 1 << 30)   # a share of a big host: its thread budget
 
 
 def test_sha512_kats(oracle):
@@ -120,32 +120,19 @@ def test_seeded_batch_digests(oracle, n):
     assert seeded_digests(oracle, int(n), THREADS) == DIG[n]
 
 
-def test_against_reference_build(oracle, reference):
-    """Direct differential test against the real reference library (only where oracle/_ref exists)."""
-    n = 384
-    sk = synth.random_bytes((n, 32), 0xD1FF01)
-    pk = synth.random_bytes((n, 32), 0xD1FF02)
-    pk[:8] = 0xff                                   # 2^256-1 rows
-    a, b = oracle.x25519_shared(pk, sk), reference.x25519_shared(pk, sk)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-    for fast in (False, True):
-        assert np.array_equal(oracle.x25519_public(sk, fast=fast)[0], reference.x25519_public(sk, fast=fast)[0])
-    pub, priv = oracle.ed25519_keypair(sk)
-    rpub, rpriv = reference.ed25519_keypair(sk)
-    assert np.array_equal(pub, rpub) and np.array_equal(priv, rpriv)
-    for mlen in (0, 1, 32, 100, 200):
-        msg = synth.random_bytes((n, mlen), 0xD1FF03 + mlen)
-        sig = oracle.ed25519_sign(priv, msg)
-        assert np.array_equal(sig, reference.ed25519_sign(priv, msg)), mlen
-        bad = sig.copy()
-        bad[::3, 7] ^= 4
-        assert np.array_equal(oracle.ed25519_verify(bad, pub, msg), reference.ed25519_verify(bad, pub, msg))
-    # garbage keys and signatures: no validation anywhere, verdicts must still agree
-    gs, gp = synth.random_bytes((n, 64), 11), synth.random_bytes((n, 32), 12)
-    msg = synth.random_bytes((n, 32), 13)
-    assert np.array_equal(oracle.ed25519_verify(gs, gp, msg), reference.ed25519_verify(gs, gp, msg))
-    assert np.array_equal(oracle.base_table(), reference.base_table())
-    # Verify_Init tables, valid keys and unvalidated garbage (off-curve "points": the values then depend on the
-    # exact order of doublings / additions, so this pins the operation sequence, not just the group element)
-    keys = np.concatenate([pub[:6], gp[:10], np.zeros((1, 32), np.uint8), np.full((1, 32), 0xff, np.uint8)])
-    assert oracle.verify_init_table(keys) == reference.verify_init_table(keys)
+def test_against_reference_build(oracle):
+    """Differential test against the real reference library: the oracle's outputs on vectors.reference_differential's
+    seeded inputs equal the reference's, stored in golden/reference_diff.npz -- and, where oracle/_ref is present, the
+    live reference still computes exactly that file."""
+    from oracle_lib import Reference
+    from vectors import reference_differential
+    with np.load(os.path.join(GOLD, "reference_diff.npz")) as f:
+        want = {k: f[k] for k in f.files}
+    got = reference_differential(oracle)
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+    if Reference.available():
+        live = reference_differential(Reference())
+        for k in want:
+            assert np.array_equal(live[k], want[k]), k

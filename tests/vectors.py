@@ -318,3 +318,39 @@ def degenerate_signature_cases():
                     put(Rb, S, Ab, m, lab)
     f = lambda rows: np.stack([np.frombuffer(x, np.uint8) for x in rows])  # noqa: E731
     return f(sigs), f(pks), f(msgs), np.array(labels, np.int32)
+
+
+def reference_differential(engine):
+    """The seeded inputs of test_oracle_golden.test_against_reference_build through `engine` (the oracle, or the real
+    reference, whose outputs tests/golden/reference_diff.npz holds): X25519 shared keys (2^256-1 peer keys included) and
+    public keys, Ed25519 key pairs, signatures of 0..200-byte messages, verdicts on corrupted signatures and on unvalidated
+    garbage, the 8-fold base table and Verify_Init tables (reduced mod p, 32 little-endian bytes per value).
+    Returns {name: uint8 / int32 array}."""
+    n = 384
+    sk = synth.random_bytes((n, 32), 0xD1FF01)
+    pk = synth.random_bytes((n, 32), 0xD1FF02)
+    pk[:8] = 0xff                                   # 2^256-1 rows
+    out = {}
+    out["x_shared"], out["x_sk_clamped"] = engine.x25519_shared(pk, sk)
+    for fast in (False, True):
+        out["x_public" + ("_fast" if fast else "")] = engine.x25519_public(sk, fast=fast)[0]
+    pub, priv = engine.ed25519_keypair(sk)
+    out["ed_pub"], out["ed_priv"] = pub, priv
+    for mlen in (0, 1, 32, 100, 200):
+        msg = synth.random_bytes((n, mlen), 0xD1FF03 + mlen)
+        sig = engine.ed25519_sign(priv, msg)
+        out[f"ed_sig_{mlen}"] = sig
+        bad = sig.copy()
+        bad[::3, 7] ^= 4
+        out[f"ed_verify_{mlen}"] = np.asarray(engine.ed25519_verify(bad, pub, msg), np.int32)
+    # garbage keys and signatures: no validation anywhere, verdicts must still agree
+    gs, gp = synth.random_bytes((n, 64), 11), synth.random_bytes((n, 32), 12)
+    msg = synth.random_bytes((n, 32), 13)
+    out["garbage_verify"] = np.asarray(engine.ed25519_verify(gs, gp, msg), np.int32)
+    out["base_table"] = engine.base_table()
+    # Verify_Init tables, valid keys and unvalidated garbage (off-curve "points": the values then depend on the
+    # exact order of doublings / additions, so this pins the operation sequence, not just the group element)
+    keys = np.concatenate([pub[:6], gp[:10], np.zeros((1, 32), np.uint8), np.full((1, 32), 0xff, np.uint8)])
+    out["verify_init_table"] = np.array([[[le(v, 32) for v in row] for row in tab] for tab in engine.verify_init_table(keys)],
+                                        np.uint8)
+    return {k: np.asarray(v) for k, v in out.items()}
