@@ -423,5 +423,41 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
     if (lane == 0) verdict[e] = (neutral & f & FLAG_R_OK) ? 1 : 0;
 }
 
+// raw-limb hook (lanes.cuh: LIMB_IN_WORDS / LIMB_OUT_WORDS), one record per wave: row r starts from input element r, limb per lane;
+// element 4 is the base point's x in SLOT_X1; output element r is row r's value afterwards.  lds: LDS_WORDS.
+//   0 a bare product level: row r multiplies element r by element 4 + r    1 carry_small of the column sums S = element r + 2^32 element 4 + r
+//   2 / 3 ladder_step<false / true>, eq = the control word    4 mont_double    5 ge_dbl    6 ge_add_pe of the row (ypx, ymx, t2d, z2) =
+//   elements 4..7, negated when the control word is nonzero
+C25519_DEV void limb_selftest_op(u32* lds, const Lane& L, u32* out, const u32* in, int op)
+{
+    const u32 c = L.c < 10 ? L.c : 0u, ctl = in[80];
+    const u32 hi = in[40 + 10 * L.row + c];
+    u32 v = in[10 * L.row + c];
+    setup_one(lds, L);
+    put_y(lds, L, SLOT_X1, in[40 + c]);
+    switch (op) {
+    case 0: put_a(lds, L, L.row, v); put_y(lds, L, 4 + L.row, hi); v = mul_level(lds, L, L.row, 4 + L.row); break;
+    case 1: v = carry_small(L, pair64(v, hi)); break;
+    case 2: v = ladder_step<false>(lds, L, v, ctl); break;
+    case 3: v = ladder_step<true>(lds, L, v, ctl); break;
+    case 4: v = mont_double(lds, L, v); break;
+    case 5: v = ge_dbl(lds, L, v); break;
+    default: put_y(lds, L, 4 + L.row, hi); v = ge_add_pe(lds, L, v, 4, ctl); break;
+    }
+    if (L.c < 10) out[10 * L.row + L.c] = v;
+    wave_fence();
+    put_a(lds, L, L.row, v);
+    wave_fence();
+    if (L.c == 0) {
+        fe f;
+        u32 w[8];
+        get_fe(f, lds, L.row);
+        fe_to_words(w, f);
+#pragma unroll
+        for (int j = 0; j < 8; j++) out[40 + 8 * L.row + j] = w[j];
+    }
+    wave_fence();
+}
+
 }  // namespace coop
 }  // namespace c25519

@@ -30,6 +30,29 @@ __global__ void __launch_bounds__(64) k_fe_selftest_quad(void* out, const void* 
     if ((threadIdx.x & 3) == 0) store32(out, i, ow);
 }
 
+// the raw-limb hooks (lanes.cuh: fe_limb_selftest_op; quad25519.cuh / coop_ops.cuh: limb_selftest_op): a lane, a quad or a wave per record
+__global__ void __launch_bounds__(64) k_fe_limb_selftest(u32* out, const u32* in, size_t n, int op)
+{
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    fe_limb_selftest_op(out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+}
+
+__global__ void __launch_bounds__(64) k_quad_limb_selftest(u32* out, const u32* in, size_t n, int op)
+{
+    const size_t i = (size_t)blockIdx.x * 16 + (threadIdx.x >> 2);
+    if (i >= n) return;                                   // (whole quads leave)
+    quad::limb_selftest_op(out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+}
+
+__global__ void __launch_bounds__(64) k_wave_limb_selftest(u32* out, const u32* in, size_t n, int op)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[coop::LDS_WORDS];
+    const size_t i = blockIdx.x;
+    if (i >= n) return;
+    coop::limb_selftest_op(lds, coop::make_lane(threadIdx.x), out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+}
+
 __global__ void __launch_bounds__(64) k_sc_selftest(void* out, const void* a, const void* b, size_t n, int op)
 {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -200,6 +223,27 @@ int c25519_amd_fe_selftest(unsigned char* out, const unsigned char* a, const uns
                          return 0;
                      });
 }
+
+// shape 0: one lane per record, 1: a quad, 2: a wave
+static int limb_selftest(unsigned* out, const unsigned* in, size_t n, int op, int shape, int ops)
+{
+    if (!out || !in) return bad_arg("null pointer");
+    if (op < 0 || op >= ops) return bad_arg("limb self-test: no such op");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ in, nullptr, 4 * LIMB_IN_WORDS }, Arr{ nullptr, out, 4 * LIMB_OUT_WORDS } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         u32* o = static_cast<u32*>(d[1]);
+                         const u32* a = static_cast<const u32*>(d[0]);
+                         if (shape == 0) k_fe_limb_selftest<<<grid_for(c, 64), 64, 0, st>>>(o, a, c, op);
+                         else if (shape == 1) k_quad_limb_selftest<<<grid_for(c, 16), 64, 0, st>>>(o, a, c, op);
+                         else k_wave_limb_selftest<<<(unsigned)c, 64, 0, st>>>(o, a, c, op);
+                         C25519_TRY(hipGetLastError());
+                         return 0;
+                     });
+}
+int c25519_amd_fe_limb_selftest(unsigned* out, const unsigned* in, size_t n, int op) { return limb_selftest(out, in, n, op, 0, 19); }
+int c25519_amd_quad_limb_selftest(unsigned* out, const unsigned* in, size_t n, int op) { return limb_selftest(out, in, n, op, 1, 4); }
+int c25519_amd_wave_limb_selftest(unsigned* out, const unsigned* in, size_t n, int op) { return limb_selftest(out, in, n, op, 2, 7); }
 
 int c25519_amd_sc_selftest(unsigned char* out, const unsigned char* a, const unsigned char* b, size_t n, int op)
 {

@@ -372,6 +372,85 @@ C25519_DEV void fe_selftest_op(u32 (&ow)[8], const u32 (&aw)[8], const u32 (&bw)
     fe_to_words(ow, r);
 }
 
+// ---- raw-limb hooks (include/curve25519_amd.h: c25519_amd_*_limb_selftest): limb vectors in, limb vectors out, no
+// fe_from_words on the way in -- so the operands can sit at the bound contract's limits (tests/test_field_limits.py).
+// A record in: eight field elements as 10 limbs each (words 0..79), then a control word (80: a ladder step's eq, an
+// addition's sign) and three words of padding.  A record out: four field elements' limbs (words 0..39), then the same
+// four as canonical words (40..71, fe_to_words); what an op does not produce is zero.
+constexpr int LIMB_IN_WORDS = 84, LIMB_OUT_WORDS = 72;
+
+C25519_DEV void limb_load(fe& f, const u32* in, int k)
+{
+#pragma unroll
+    for (int j = 0; j < 10; j++) f.v[j] = in[10 * k + j];
+}
+C25519_DEV void limb_store(u32* out, int k, const fe& f)
+{
+    u32 w[8];
+    fe_to_words(w, f);
+#pragma unroll
+    for (int j = 0; j < 10; j++) out[10 * k + j] = f.v[j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[40 + 8 * k + j] = w[j];
+}
+
+// one lane.  x, y, z = input elements 0, 1, 2
+//   0 x*y (fe_mul)   1 fe_mul_runs   2 x^2 (fe_sqr)   3 fe_sqr_runs   4 x^2 - y (fe_sqr_sub)   5 2x^2 + y - z (fe_sqr2_add_sub)
+//   6 x + 121665 y   7 9x (fe_mul_small)   8 fe_carry32(x)   9 x + y   10 x - y   11 -x   12 x as it is (fe_to_words alone)
+//   13 1/x (fe_invert)   14 / 15 ladder_step<false / true> on (SX, SZ, DX, DZ) = elements 0..3, base = element 4, eq = control
+//   16 ge_double on (X, Y, Z, T) = 0..3   17 ge_add_pa of (ypx, ymx, t2d) = 4..6   18 ge_add_pe of (ypx, ymx, t2d, z2) = 4..7
+C25519_DEV void fe_limb_selftest_op(u32* out, const u32* in, int op)
+{
+    fe x, y, z, r;
+    const u32 ctl = in[80];
+    if (op >= 14) {
+        ge_ext p;
+        limb_load(p.X, in, 0); limb_load(p.Y, in, 1); limb_load(p.Z, in, 2); limb_load(p.T, in, 3);
+        if (op == 14 || op == 15) {
+            limb_load(x, in, 4);
+            if (op == 14) ladder_step<false>(p.X, p.Y, p.Z, p.T, x, ctl);
+            else ladder_step<true>(p.X, p.Y, p.Z, p.T, x, ctl);
+        } else if (op == 16) {
+            ge_double(p);
+        } else if (op == 17) {
+            ge_pa q;
+            limb_load(q.ypx, in, 4); limb_load(q.ymx, in, 5); limb_load(q.t2d, in, 6);
+            ge_add_pa(p, q);
+        } else {
+            ge_pe q;
+            limb_load(q.ypx, in, 4); limb_load(q.ymx, in, 5); limb_load(q.t2d, in, 6); limb_load(q.z2, in, 7);
+            ge_ext s;
+            ge_add_pe(s, p, q);
+            p = s;
+        }
+        limb_store(out, 0, p.X); limb_store(out, 1, p.Y); limb_store(out, 2, p.Z); limb_store(out, 3, p.T);
+        return;
+    }
+    limb_load(x, in, 0);
+    limb_load(y, in, 1);
+    limb_load(z, in, 2);
+    switch (op) {
+    case 0: fe_mul(r, x, y); break;
+    case 1: fe_mul_runs(r, x, y); break;
+    case 2: fe_sqr(r, x); break;
+    case 3: fe_sqr_runs(r, x); break;
+    case 4: fe_sqr_sub(r, x, y); break;
+    case 5: fe_sqr2_add_sub(r, x, y, z); break;
+    case 6: fe_mul121665_add(r, x, y); break;
+    case 7: fe_mul_small(r, x, 9); break;
+    case 8: fe_carry32(r, x); break;
+    case 9: fe_add(r, x, y); break;
+    case 10: fe_sub(r, x, y); break;
+    case 11: fe_neg(r, x); break;
+    case 13: fe_invert(r, x); break;
+    default: r = x; break;
+    }
+    fe_set_u32(x, 0);
+    limb_store(out, 0, r);
+#pragma unroll 1
+    for (int k = 1; k < 4; k++) limb_store(out, k, x);
+}
+
 // scalar hook (mod L): the device side of the reference's eco_* unit checks (test/curve25519_selftest.c:624-714).
 // a = 16 words (512 bits), b = 8 words; "raw" results are 256 bits congruent to the exact value mod L.
 //   0 canonical(a mod L)            sc_reduce512 + sc_mod          (eco_DigestToWords + eco_Mod)

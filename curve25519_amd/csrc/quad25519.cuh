@@ -538,5 +538,27 @@ C25519_DEV void verify_check_wide_element(int* verdict, const void* sig, const u
     if (R.is0) verdict[e] = diff == 0 ? 1 : 0;
 }
 
+// raw-limb hook (lanes.cuh: LIMB_IN_WORDS / LIMB_OUT_WORDS), one record per quad: input elements 0..3 are lane q's `own`, element 4
+// the base point's x of a ladder step, element 4 + q lane q's `mult` of an addition, the control word a ladder step's eq; output
+// element q is lane q's `own` afterwards.   op 0 / 1 ladder_step<false / true>   2 ge_add_fields   3 ge_double
+C25519_DEV void limb_selftest_op(u32* out, const u32* in, int op)
+{
+    const Roles R = roles();
+    const int q = (int)(threadIdx.x & 3u);
+    fe own, aux;
+    limb_load(own, in, q);
+    if (op == 0 || op == 1) {
+        limb_load(aux, in, 4);
+        if (op == 0) ladder_step<false>(own, aux, in[80], R);
+        else ladder_step<true>(own, aux, in[80], R);
+    } else if (op == 2) {
+        limb_load(aux, in, 4 + q);
+        ge_add_fields(own, aux, R);
+    } else {
+        ge_double(own, R);
+    }
+    limb_store(out, q, own);
+}
+
 }  // namespace quad
 }  // namespace c25519

@@ -223,6 +223,17 @@ int c25519_amd_verify_point_dev(void *out, const void *sig, const void *pk, cons
  * The unit-test hook for the L0 layer (the reference's ECP_SELF_TEST checks, test/curve25519_selftest.c:640-741). */
 int c25519_amd_fe_selftest(unsigned char *out, const unsigned char *a, const unsigned char *b, size_t n, int op);
 
+/* the same field code on raw limb vectors (host pointers): no conversion from bytes on the way in, so a test can put every
+ * operand at the limits of the limb bound contract (csrc/fe25519.cuh).  A record in is 84 words: eight field elements as ten
+ * 32-bit limbs each (radix 2^25.5), a control word, three words of padding; a record out is 72 words: four field elements'
+ * limbs, then the same four as canonical little-endian words.  The ops are listed at their definitions:
+ *   fe_limb_selftest     one lane per record (csrc/lanes.cuh: fe_limb_selftest_op, ops 0..18)
+ *   quad_limb_selftest   four lanes per record (csrc/quad25519.cuh: quad::limb_selftest_op, ops 0..3)
+ *   wave_limb_selftest   one wave per record (csrc/coop_ops.cuh: coop::limb_selftest_op, ops 0..6) */
+int c25519_amd_fe_limb_selftest(unsigned *out, const unsigned *in, size_t n, int op);
+int c25519_amd_quad_limb_selftest(unsigned *out, const unsigned *in, size_t n, int op);
+int c25519_amd_wave_limb_selftest(unsigned *out, const unsigned *in, size_t n, int op);
+
 /* device scalar arithmetic mod L (reference source/curve25519_order.c, unit checks test/curve25519_selftest.c:624-714):
  * a is n x 64 bytes (512-bit little-endian), b n x 32 bytes, out n x 32 bytes.
  *   op 0 canonical(a mod L)   1 raw a mod L            2 canonical(a[0..31] mod L)   3 raw a[0..31]*b

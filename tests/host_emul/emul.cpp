@@ -597,6 +597,34 @@ static void emul_fe_op_quad(unsigned char* out, const unsigned char* a, const un
         });
 }
 
+// ---- the raw-limb hooks (include/curve25519_amd.h: c25519_amd_*_limb_selftest), records of LIMB_IN_WORDS in, LIMB_OUT_WORDS out;
+// the kernels of engine_api.hip are the same indexing around the same calls
+void emul_fe_limb_op(unsigned* out, const unsigned* in, size_t n, int op)
+{
+    for (size_t i = 0; i < n; i++) fe_limb_selftest_op(out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+}
+
+void emul_quad_limb_op(unsigned* out, const unsigned* in, size_t n, int op)
+{
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    for (size_t base = 0; base < n; base += quad::ELEMS_PER_WAVE)
+        emul_coop::run_block(64, [&] {
+            const size_t i = base + (threadIdx.x >> 2);
+            if (i >= n) return;
+            quad::limb_selftest_op(out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+        });
+}
+
+void emul_wave_limb_op(unsigned* out, const unsigned* in, size_t n, int op)
+{
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    std::vector<u32> lds(coop::LDS_WORDS);
+    for (size_t i = 0; i < n; i++)
+        emul_coop::run_block(64, [&] {
+            coop::limb_selftest_op(lds.data(), coop::make_lane(threadIdx.x), out + i * LIMB_OUT_WORDS, in + i * LIMB_IN_WORDS, op);
+        });
+}
+
 // ---- four lanes per element (csrc/quad25519.cuh): a wave of 64 lock-step lanes carries 16 elements; the kernel is
 // `e = blockIdx.x * 16 + lane / 4; if (e >= n) return;` around the call below
 void emul_quad_x25519(unsigned char* out, const unsigned char* pk, unsigned char* sk, size_t n)

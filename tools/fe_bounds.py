@@ -4,9 +4,12 @@
 The device field code keeps ten unsaturated limbs (radix 2^25.5) in 32-bit registers and 64-bit column
 accumulators; it is only correct if no 32-bit operand, no 64-bit column and no biased subtraction ever
 overflows / goes negative -- for ALL inputs, not just the random ones the parity tests throw at it.  This
-script replays the formulas of x25519.cuh / ge25519.cuh / engine.hip on per-limb upper bounds (interval
-arithmetic with exact Python integers) and asserts every such condition, starting from the worst inputs the
-contract allows ("reduced" = whatever a mul/sqr carry chain can emit).  Run: python tools/fe_bounds.py
+script replays the formulas of x25519.cuh / ge25519.cuh / engine.hip, and those of the four-lane (quad25519.cuh) and
+one-wave (coop25519.cuh) shapes, on per-limb upper bounds (interval arithmetic with exact Python integers; a per-lane
+choice is the larger of its two sides) and asserts every such condition, starting from the worst inputs the contract
+allows ("reduced" = whatever a mul/sqr carry chain, of either shape, can emit).  coop25519.cuh's carry_small has an output
+class of its own (coop_small_class), checked at each of its consumers.  tests/limb_vectors.py builds the edge inputs of
+the raw-limb tests from CONTRACT and these classes.  Run: python tools/fe_bounds.py
 """
 M26, M25 = (1 << 26) - 1, (1 << 25) - 1
 W = [26, 25] * 5
@@ -183,17 +186,35 @@ ONE = [1] + [0] * 9
 CANON = list(MASK)
 
 
+# the documented operand limits of fe25519.cuh's contract, as beta = limb / 2^w (tests/limb_vectors.py builds its edge inputs from
+# these too, so the proof and the tests cannot drift apart)
+CONTRACT = {
+    "mul_a": 5, "mul_b": 3.3,          # fe_mul
+    "sqr": 3.3,                        # fe_sqr, fe_sqr_sub's a
+    "sqr_sub_m": 2,                    # fe_sqr_sub's m (bias 4p)
+    "sqr2": 2.3,                       # fe_sqr2_add_sub's a (columns doubled)
+    "small": 7.9,                      # fe_mul121665_add, fe_mul_small: any beta < 8
+    "carry32": 63,                     # fe_carry32: any beta < 2^6
+}
+
+
+def at_beta(beta):
+    """Every limb at beta * 2^w (the largest limb vector of that class)."""
+    return [int(beta * (1 << W[i])) for i in range(10)]
+
+
 def reduced_fixpoint():
     """Largest limbs any carry chain can emit, iterated until stable."""
     red = list(FROM_WORDS)
-    big = [U32 // 19 if True else 0 for _ in range(10)]
-    del big
     for _ in range(4):
-        worst_in_a = [5 * (1 << W[i]) for i in range(10)]
-        worst_in_b = [int(3.3 * (1 << W[i])) for i in range(10)]
-        cands = [mul(worst_in_a, worst_in_b, "contract mul"), sqr(worst_in_b, "contract sqr"),
-                 carry32([50 * (1 << W[i]) for i in range(10)], "contract carry32"),
-                 mul121665_add(worst_in_a, worst_in_a, "contract a24")]
+        worst_in_a = at_beta(CONTRACT["mul_a"])
+        worst_in_b = at_beta(CONTRACT["mul_b"])
+        cands = [mul(worst_in_a, worst_in_b, "contract mul"), sqr(at_beta(CONTRACT["sqr"]), "contract sqr"),
+                 carry32(at_beta(CONTRACT["carry32"]), "contract carry32"),
+                 mul121665_add(at_beta(CONTRACT["small"]), at_beta(CONTRACT["small"]), "contract a24"),
+                 chained_small_mul(at_beta(CONTRACT["small"]), 9, [0] * 10, "contract mul_small"),
+                 # coop25519.cuh's product: its last carry pass leaves limbs up to 2^w + 1 (fe25519.cuh's chain masks them exactly)
+                 coop_carry(coop_columns(worst_in_a, worst_in_b, "contract coop product"), "contract coop product")]
         new = [max([red[i]] + [c[i] for c in cands]) for i in range(10)]
         if new == red:
             break
@@ -218,6 +239,209 @@ def chain250(x, R):
     sqr(R, "chain sqr")
     mul(R, x, "chain final mul by x")
     return R
+
+
+# ---- quad25519.cuh: four lanes per element; every per-lane choice (q_sel, a role mask) is a select ----------------------------
+def quad_ladder_step(own, x1, base9, deeper=0):
+    """quad::ladder_step on `own` (every lane's), x1 the base point's x.  deeper: extra q_sub levels on the level-2 operands
+    (the bite test's knob)."""
+    s, d = add(own, own, "quad l1 sum"), sub(own, own, "quad l1 diff")
+    give, keep = select(d, s), select(s, d)
+    got = give
+    a, b = select(keep, got), select(keep, got)
+    p = mul(a, b, "quad level 1")
+    other = p
+    s, d = add(p, other, "quad l2 sum"), sub(p, other, "quad l2 diff")
+    keep = neg(other, "quad l2 -AA")
+    got = mul121665_add(keep, d, "quad l2 a24")
+    give = select(s, d)
+    a = select(p, give)
+    b = select(other, select(got, give))
+    for _ in range(deeper):
+        a, b = sub(a, R_QUAD, "deeper"), sub(b, R_QUAD, "deeper")
+    p = mul(a, b, "quad level 2")
+    a = chained_small_mul(p, 9, [0] * 10, "quad level 3 (times 9)") if base9 else mul(p, x1, "quad level 3")
+    return select(a, p)
+
+
+def quad_mult_field():
+    """The `mult` of ge_add_fields: a row field from words or the LDS comb, negated by q_neg on q2 (beta 2), or the constant 2."""
+    f = FROM_WORDS
+    return select(select(neg(f, "row_field_unpack q_neg"), f), [2] + [0] * 9)
+
+
+def quad_ge_add_fields(own, mult):
+    s, d = add(own, own, "quad add Y+X"), sub(own, own, "quad add Y-X")
+    a = select(d, select(s, own))
+    p = mul(a, mult, "quad add level 1")
+    s, d = add(p, p, "quad add h, g"), sub(p, p, "quad add e, f")
+    a = select(s, select(d, d))
+    b = select(d, select(s, s))
+    return mul(a, b, "quad add level 2")
+
+
+def quad_ge_double(own):
+    s = add(own, own, "quad dbl X+Y")
+    p = sqr(select(s, own), "quad dbl level 1")
+    s, d = add(p, p, "quad dbl Hn"), sub(p, p, "quad dbl G")
+    F = select(d, s)
+    need(all(F[i] <= 2 * P2[i] for i in range(10)), "quad dbl: 4p bias smaller than the subtrahend")
+    u = [p[i] + p[i] + 2 * P2[i] for i in range(10)]      # p + (p & is3) + 4p - F
+    need(all(x <= U32 for x in u), "quad dbl: u overflows 32 bits")
+    u = carry32(u, "quad dbl u")
+    a = select(u, select(d, F))
+    b = select(u, select(s, u))
+    return mul(a, b, "quad dbl level 2")
+
+
+# ---- coop25519.cuh: a field element limb per lane, a product as one column per lane -------------------------------------------
+def coop_put_y(b, where):
+    """put_y: the multiplier pre-scaled in 32 bits -- yo = 19 b, ye = 38 b for an odd limb, 19 b for an even one."""
+    for j in range(10):
+        need(19 * b[j] <= U32, f"{where}: 19*b overflows 32 bits (limb {j})")
+        need((19 * b[j]) << (j & 1) <= U32, f"{where}: 38*b overflows 32 bits (limb {j})")
+        need(b[j] << (j & 1) <= U32, f"{where}: 2*b overflows 32 bits (limb {j})")
+
+
+def coop_columns(a, b, where):
+    """coop::column: lane c's ten-term sum a_(9-t) * (yo or ye)[c+1+t]."""
+    coop_put_y(b, where)
+    yo = [19 * x for x in b] + list(b)
+    ye = [(19 * b[j]) << (j & 1) for j in range(10)] + [b[j] << (j & 1) for j in range(10)]
+    S = []
+    for c in range(10):
+        acc = sum(a[9 - t] * (yo[c + 1 + t] if t & 1 else ye[c + 1 + t]) for t in range(10))
+        need(acc <= U64, f"{where}: column {c} overflows 64 bits")
+        S.append(acc)
+    return S
+
+
+def coop_carry(S, where):
+    """coop::carry / carry_packed (row_carry): S = l0 + 2^w l1 + 2^51 l2, limb_c = l0_c + l1_(c-1) + l2_(c-2) (19 x around the
+    wrap), then one more pass of the bits above w."""
+    need(all(x <= U64 for x in S), f"{where}: column sum overflows 64 bits")
+    l0 = [min(S[c], MASK[c]) for c in range(10)]
+    l1 = [min(S[c] >> W[c], MASK[(c + 1) % 10]) for c in range(10)]
+    l2 = [S[c] >> 51 for c in range(10)]
+    limb = []
+    for c in range(10):
+        x = l0[c] + (l1[c - 1] if c >= 1 else 19 * l1[9]) + (l2[c - 2] if c >= 2 else 19 * l2[c + 8])
+        need(x <= U32, f"{where}: carried limb {c} overflows 32 bits")
+        limb.append(x)
+    e = [limb[c] >> W[c] for c in range(10)]
+    out = [min(limb[c], MASK[c]) + (e[c - 1] if c else 19 * e[9]) for c in range(10)]
+    need(all(x <= U32 for x in out), f"{where}: limb exceeds 32 bits")
+    return out
+
+
+CARRY_SMALL_IN = 1 << 46
+
+
+def carry_small(S, where):
+    """coop::carry_small: one piece moves up.  Precondition S < 2^46; out_c = (S_c & mask) + (S_(c-1) >> w), 19 x at the wrap."""
+    need(all(x < CARRY_SMALL_IN for x in S), f"{where}: carry_small input reaches 2^46")
+    out = [min(S[c], MASK[c]) + ((S[c - 1] >> W[c - 1]) if c else 19 * (S[9] >> 25)) for c in range(10)]
+    need(all(x <= U32 for x in out), f"{where}: carry_small limb exceeds 32 bits")
+    SMALL_SEEN.append(out)
+    return out
+
+
+SMALL_SEEN = []
+
+
+def mul_level(a, b, where):
+    return coop_carry(coop_columns(a, b, where), where)
+
+
+def coop_small_class():
+    """The named limb class of carry_small's outputs: the largest each limb reaches over every call site replayed so far."""
+    return [max(v[i] for v in SMALL_SEEN) for i in range(10)]
+
+
+def coop_ladder_step(v, x1, base9):
+    val = select(sub(v, v, "coop ladder diff"), add(v, v, "coop ladder sum"))
+    v = mul_level(val, val, "coop ladder level 1")                     # A Dp, C B, P^2, M^2 (sel is one of val's rows)
+    d2 = sub(v, v, "coop ladder d2")
+    base = select(d2, select(v, add(v, v, "coop ladder DA+CB")))
+    w = carry_small(select([x * 121665 + y for x, y in zip(d2, v)], base), "coop ladder phase 1.5")
+    x = select(v, w)
+    v = mul_level(x, x, "coop ladder level 2")
+    if base9:
+        return coop_carry([9 * y for y in v], "coop ladder times 9 (carry_packed)")
+    return mul_level(v, select(ONE, x1), "coop ladder level 3")
+
+
+def coop_mont_double(v):
+    val = select(sub(v, v, "coop dbl x-z"), add(v, v, "coop dbl x+z"))
+    v = mul_level(val, val, "coop dbl level 1")
+    E = sub(v, v, "coop dbl E")
+    F = carry_small([x * 121665 + y for x, y in zip(E, v)], "coop dbl F")
+    return mul_level(select(E, v), select(F, v), "coop dbl level 2")
+
+
+def coop_ladder2(v):
+    """ladder2_step_sum (wave 0) and ladder2_step_double (wave 1)."""
+    val = select(sub(v, v, "coop2 sum A"), add(v, v, "coop2 sum B"))
+    p = mul_level(val, val, "coop2 sum level 1")
+    w = carry_small(select(add(p, p, "coop2 V"), sub(p, p, "coop2 U")), "coop2 sum V, U")
+    s = mul_level(w, w, "coop2 sum level 2")
+    return s, coop_mont_double(v)
+
+
+def coop_ge_add_finish(v):
+    w = select(add(v, v, "coop add h, g"), sub(v, v, "coop add e, f"))
+    return mul_level(w, w, "coop add level 2")
+
+
+def coop_ge_add(v, q):
+    op = select(select(v, add(v, v, "coop add 2Z, Y+X")), sub(v, v, "coop add Y-X"))
+    return coop_ge_add_finish(mul_level(op, select(q, ONE), "coop add level 1"))
+
+
+def coop_ge_add_pe(v, q):
+    t = select(neg(v, "coop add_pe -T"), v)
+    op = select(select(t, add(v, v, "coop add_pe Y+X")), sub(v, v, "coop add_pe Y-X"))
+    return coop_ge_add_finish(mul_level(op, q, "coop add_pe level 1"))
+
+
+def coop_ge_dbl(v):
+    x = select(v, add(v, v, "coop dbl X+Y"))
+    p = mul_level(x, x, "coop ge_dbl level 1")
+    hg = select(sub(p, p, "coop ge_dbl G"), add(p, p, "coop ge_dbl Hn"))
+    need(all(hg[i] <= 2 * P2[i] for i in range(10)), "coop ge_dbl: 4p bias smaller than the subtrahend")
+    up = [2 * p[i] + 2 * P2[i] for i in range(10)]
+    need(all(y <= U32 for y in up), "coop ge_dbl: 2 Z^2 + 4p overflows 32 bits")
+    w = carry_small(select(up, hg), "coop ge_dbl E, Fn")
+    return mul_level(w, w, "coop ge_dbl level 2")
+
+
+def quad_section(R):
+    for base9 in (False, True):
+        need(all(x <= r for x, r in zip(quad_ladder_step(R, FROM_WORDS, base9), R)), "quad ladder output not reduced")
+    need(all(x <= r for x, r in zip(quad_ge_add_fields(R, quad_mult_field()), R)), "quad addition output not reduced")
+    need(all(x <= r for x, r in zip(quad_ge_double(R), R)), "quad doubling output not reduced")
+    # engine_common.cuh: the shared inversion's quad exchange -- pair = acc * partner, total = pair * other pair, then 1/total times both
+    pair = mul(R, R, "batch invert pair")
+    total = mul(pair, pair, "batch invert total")
+    inv = mul(mul(R, pair, "batch invert x other pair"), R, "batch invert x partner")
+    for v in (pair, total, inv):
+        need(all(x <= r for x, r in zip(v, R)), "batch invert output not reduced")
+
+
+def coop_section(R):
+    del SMALL_SEEN[:]
+    outs = [coop_ladder_step(R, FROM_WORDS, False), coop_ladder_step(R, FROM_WORDS, True), coop_mont_double(R), *coop_ladder2(R),
+            coop_ge_add(R, select(P2, FROM_WORDS)), coop_ge_add_pe(R, select(R, P2)), coop_ge_dbl(R)]
+    for v in outs:
+        need(all(x <= r for x, r in zip(v, R)), "coop output not reduced: loop invariant broken")
+    small = coop_small_class()
+    # every consumer of a carry_small output is a product operand, first or second (put_a and put_y): within the contract
+    need(all(small[i] <= at_beta(CONTRACT["mul_b"])[i] for i in range(10)), "carry_small output too large for a product operand")
+    mul_level(small, small, "carry_small output as both factors")
+    return small
+
+
+R_QUAD = reduced_fixpoint()
 
 
 def main():
@@ -352,6 +576,11 @@ def main():
     mul(t2d_neg, CANON, "signed comb: ge_from_pa T of a negated first row")
     carry32(neg(CANON, "signed comb table generation: -B's 2dxy"))
     print("lattice verification walk, signed comb and blinded base walk: ok")
+    quad_section(R)
+    print("quad25519 ladder step, addition, doubling, batch-inversion exchange: ok")
+    small = coop_section(R)
+    print(f"coop25519 carry_small output class: beta <= {beta(small):.6f} (limb0 <= 2^26 + {small[0] - (1 << 26)})")
+    print("coop25519 products, carries, ladder, two-wave ladder, mont_double, edwards add / double: ok")
     print("all bounds hold")
 
 
