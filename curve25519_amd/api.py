@@ -51,6 +51,19 @@ def curve25519_dh_CreateSharedKey(pk, sk):
     return out, sk
 
 
+def curve25519_dh_CreateSharedKey_one_peer(pk, sk):
+    """n x curve25519_dh_CreateSharedKey with ONE peer key `pk` (32 bytes) for every secret.  Returns (shared, clamped_sk);
+    the same bytes as curve25519_dh_CreateSharedKey with pk repeated n times (a large call walks a comb built for the peer)."""
+    pk = _np(pk, 32, "pk")
+    if pk.shape[0] != 1:
+        raise ValueError("pk must be ONE 32-byte key")
+    sk = np.array(_np(sk, 32, "sk"), copy=True)
+    out = np.empty_like(sk)
+    _lib.check(_lib.load().curve25519_dh_CreateSharedKey_one_peer_batch(_ptr(out), _ptr(pk), _ptr(sk), sk.shape[0]),
+               "curve25519_dh_CreateSharedKey_one_peer_batch")
+    return out, sk
+
+
 def curve25519_dh_CalculatePublicKey(sk, fast=False):
     """n x curve25519_dh_CalculatePublicKey (or _fast).  Returns (pk, clamped_sk)."""
     sk = np.array(_np(sk, 32, "sk"), copy=True)
@@ -204,6 +217,17 @@ def curve25519_dh_CreateSharedKey_dev(shared, pk, sk):
     args = (_check(shared, 32, "shared", n, device=d), _check(pk, 32, "pk"), _check(sk, 32, "sk", n, device=d))
     with _on(pk) as st:
         _lib.check(_lib.load().curve25519_dh_CreateSharedKey_dev(*args, n, st), "curve25519_dh_CreateSharedKey_dev")
+
+
+def curve25519_dh_CreateSharedKey_one_peer_dev(shared, pk, sk):
+    """In-place device form with ONE peer key (`pk`: a (1, 32) or (32,) uint8 CUDA tensor): writes `shared`, clamps `sk`;
+    asynchronous on torch's current stream (the comb-or-ladder decision is taken on the device)."""
+    n, d = sk.shape[0], sk.device
+    pk = pk.reshape(1, -1) if getattr(pk, "dim", lambda: 2)() == 1 else pk
+    args = (_check(shared, 32, "shared", n, device=d), _check(pk, 32, "pk", 1, device=d),
+            _check(sk, 32, "sk"))
+    with _on(sk) as st:
+        _lib.check(_lib.load().curve25519_dh_CreateSharedKey_one_peer_dev(*args, n, st), "curve25519_dh_CreateSharedKey_one_peer_dev")
 
 
 def curve25519_dh_CalculatePublicKey_dev(pk, sk, fast=False):

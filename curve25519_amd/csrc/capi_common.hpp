@@ -94,6 +94,7 @@ enum Tunable {
     T_LADDER2_MAX,              // curve25519_dh_CreateSharedKey: largest call that runs the ladder on TWO waves per element (0: never)
     T_QUAD_MIN,                 // calls of MORE than QUAD_MIN and at most QUAD_MAX elements run FOUR LANES per element (quad25519.cuh):
     T_QUAD_MAX,                 //   QUAD_MAX = 0: never; unset: per operation (engine.hip)
+    T_ONE_PEER_WIDE,            // curve25519_dh_CreateSharedKey_one_peer: smallest batch that builds a wide comb for a NEW peer key (0: never)
     T_COUNT
 };
 constexpr long T_UNSET = -1;
@@ -101,7 +102,7 @@ inline const char* const* tunable_names()
 {
     static const char* const names[T_COUNT] = { "COOP_MAX", "XF_SPLIT", "INV_K", "VERIFY_REFERENCE_ORDER", "MULTI_FORCE_GATHER",
                                                 "MULTI_VIRTUAL", "BASE_COMB", "HELPER_THREADS", "VERIFY_LAT_CAP_BITS", "ONE_KEY_WIDE", "LADDER2_MAX",
-                                                "QUAD_MIN", "QUAD_MAX" };
+                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE" };
     return names;
 }
 inline std::atomic<long>* tunable_table()
@@ -237,6 +238,9 @@ struct ThreadState {
     void* bctx = nullptr;                  // the same for the 192-byte blinding context of this thread's last blinded *_batch call
     unsigned char bctx_host[192] = {};
     bool bctx_valid = false;
+    void* peer = nullptr;                  // ... and for the 32-byte peer key of this thread's last one-peer X25519 *_batch call
+    unsigned char peer_host[32] = {};
+    bool peer_valid = false;
     void* hbuf[SETS][SLOTS] = {};          // pinned host staging (hipHostMalloc)
     size_t hcap[SETS][SLOTS] = {};
     // The completion word of a call of ONE element (host_pipeline.hpp: zero-copy calls): pinned host memory the call's last
@@ -253,6 +257,7 @@ struct ThreadState {
     // least recently used slab and first waits for its previous use.
     static constexpr int MAX_DEV = 64;
     static constexpr int CALLER_SLABS = 4;
+    enum KeepSlot { KEEP_VERIFY, KEEP_PEER, KEEP_SLOTS };
     struct WorkSlab {
         void* ptr = nullptr;
         size_t cap = 0;
@@ -266,8 +271,10 @@ struct ThreadState {
     unsigned long work_clock = 0;
     unsigned long generation = 0;          // bumped whenever streams / slabs / report words are destroyed: a handle to one of
                                            // them remembered across calls (engine.hip: LastVerify) is stale afterwards
-    WorkSlab keep[MAX_DEV];                // per device: a buffer whose CONTENT outlives the call (the comb of the last one-key
-                                           // verification batch's key, engine.hip); same stream-order rules as a work slab
+    // per device and use: a buffer whose CONTENT outlives the call -- KEEP_VERIFY the comb of the last one-key verification
+    // batch's key, KEEP_PEER the comb of the last one-peer X25519 batch's peer key (engine.hip) -- so that the two do not evict
+    // each other; same stream-order rules as a work slab
+    WorkSlab keep[MAX_DEV][KEEP_SLOTS];
     WorkSlab lane_work[LANES];             // ... and one per pipeline lane, so that the pieces of a *_batch call do not
                                            // wait for each other's kernels (they belong to the staging device)
 
@@ -368,13 +375,13 @@ struct ThreadState {
     }
     // the persistent buffer of the current device, at least `bytes` (zero-filled when it is (re)allocated: *fresh says so);
     // a call on another stream than the last one first waits for that one's use (release_keep)
-    int acquire_keep(void** out, size_t bytes, hipStream_t s, bool* fresh)
+    int acquire_keep(void** out, size_t bytes, hipStream_t s, bool* fresh, KeepSlot slot = KEEP_VERIFY)
     {
         int dev = 0;
         C25519_TRY(hipGetDevice(&dev));
         if (dev < 0 || dev >= MAX_DEV) return bad_arg("device ordinal out of range");
         arm_exit_guard();
-        WorkSlab& w = keep[dev];
+        WorkSlab& w = keep[dev][slot];
         *fresh = false;
         if (w.ptr && bytes > w.cap) {
             C25519_TRY(hipDeviceSynchronize());
@@ -393,19 +400,19 @@ struct ThreadState {
         *out = w.ptr;
         return 0;
     }
-    int release_keep(hipStream_t s)
+    int release_keep(hipStream_t s, KeepSlot slot = KEEP_VERIFY)
     {
         int dev = 0;
         C25519_TRY(hipGetDevice(&dev));
-        C25519_TRY(hipEventRecord(keep[dev].done, s));
+        C25519_TRY(hipEventRecord(keep[dev][slot].done, s));
         return 0;
     }
     // has a call of this thread on the current device left a kept buffer behind (a key's comb and the context it belongs to)?
-    bool has_keep() const
+    bool has_keep(KeepSlot slot = KEEP_VERIFY) const
     {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
-        return keep[dev].ptr != nullptr;
+        return keep[dev][slot].ptr != nullptr;
     }
     // the report word of the slab acquire_work(…, s) handed out (call between acquire_work and release_work)
     int report_word_for(unsigned** out, hipStream_t s)
@@ -456,6 +463,8 @@ struct ThreadState {
         if (bctx) { (void)hipMemset(bctx, 0, 192); (void)hipFree(bctx); bctx = nullptr; }
         memset(bctx_host, 0, sizeof bctx_host);
         bctx_valid = false;
+        if (peer) { (void)hipFree(peer); peer = nullptr; }
+        peer_valid = false;
         for (int l = 0; l < LANES; l++) {
             free_slab(lane_work[l]);
             if (stream[l]) (void)hipStreamDestroy(stream[l]);
@@ -474,12 +483,12 @@ struct ThreadState {
         for (int d = 0; d < MAX_DEV; d++) {
             bool any = false;
             for (const WorkSlab& w : work[d]) any = any || w.ptr || w.done || w.report;
-            any = any || keep[d].ptr || keep[d].done;
+            for (const WorkSlab& k : keep[d]) any = any || k.ptr || k.done;
             if (!any) continue;
             (void)hipSetDevice(d);
             (void)hipDeviceSynchronize();
             for (WorkSlab& w : work[d]) free_slab(w);
-            free_slab(keep[d]);
+            for (WorkSlab& k : keep[d]) free_slab(k);
         }
         (void)hipGetLastError();
         if (cur >= 0) (void)hipSetDevice(cur);
@@ -530,22 +539,23 @@ public:
     KeepLease() = default;
     KeepLease(const KeepLease&) = delete;
     KeepLease& operator=(const KeepLease&) = delete;
-    ~KeepLease() { if (live_) { (void)tls().release_keep(stream_); (void)hipGetLastError(); } }
-    int acquire(void** out, size_t bytes, hipStream_t s, bool* fresh)
+    ~KeepLease() { if (live_) { (void)tls().release_keep(stream_, slot_); (void)hipGetLastError(); } }
+    int acquire(void** out, size_t bytes, hipStream_t s, bool* fresh, ThreadState::KeepSlot slot = ThreadState::KEEP_VERIFY)
     {
-        C25519_RC(tls().acquire_keep(out, bytes, s, fresh));
-        stream_ = s; live_ = true;
+        C25519_RC(tls().acquire_keep(out, bytes, s, fresh, slot));
+        stream_ = s; slot_ = slot; live_ = true;
         return 0;
     }
     int release()
     {
         if (!live_) return 0;
         live_ = false;
-        return tls().release_keep(stream_);
+        return tls().release_keep(stream_, slot_);
     }
 
 private:
     hipStream_t stream_ = nullptr;
+    ThreadState::KeepSlot slot_ = ThreadState::KEEP_VERIFY;
     bool live_ = false;
 };
 

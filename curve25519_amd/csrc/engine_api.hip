@@ -291,6 +291,29 @@ int curve25519_dh_CreateSharedKey_batch(unsigned char* shared, const unsigned ch
                      });
 }
 
+// the peer key has a device buffer of its own per calling thread, uploaded once per call -- and only when its bytes differ from
+// what the thread uploaded last -- not once per piece
+int curve25519_dh_CreateSharedKey_one_peer_batch(unsigned char* shared, const unsigned char* pk, unsigned char* sk, size_t n)
+{
+    C25519_API_CALL();
+    if (!shared || !pk || !sk) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    ThreadState& t = tls();
+    C25519_RC(t.ensure());
+    if (!t.peer) C25519_TRY(hipMalloc(&t.peer, 32));
+    void* dpk = t.peer;
+    if (!t.peer_valid || memcmp(t.peer_host, pk, 32) != 0) {
+        t.peer_valid = false;
+        C25519_RC(c25519_host::upload_now(dpk, pk, 32));
+        memcpy(t.peer_host, pk, 32);
+        t.peer_valid = true;
+    }
+    return run_batch(n, { Arr{ sk, sk, 32 }, Arr{ nullptr, shared, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return curve25519_dh_CreateSharedKey_one_peer_dev(d[1], dpk, d[0], c, st);
+                     });
+}
+
 static int public_batch(unsigned char* pk, unsigned char* sk, size_t n, bool fast)
 {
     if (!pk || !sk) return bad_arg("null pointer");

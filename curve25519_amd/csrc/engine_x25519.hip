@@ -1,7 +1,9 @@
 // curve25519_amd/csrc/engine_x25519.hip -- the X25519 kernels (the Montgomery ladder per lane, fused with the shared inversion, per wave, on two
-// waves, on quads) and curve25519_dh_CreateSharedKey_dev / curve25519_dh_CalculatePublicKey_dev
+// waves, on quads; many secrets against one peer key over that key's wide comb) and curve25519_dh_CreateSharedKey_dev /
+// curve25519_dh_CalculatePublicKey_dev / curve25519_dh_CreateSharedKey_one_peer_dev
 // (one of the engine's four translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
+#include "x25519_peer.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // X25519   (curve25519_dh_CreateSharedKey / curve25519_dh_CalculatePublicKey)
@@ -244,6 +246,152 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
     quad::x25519_element<BASE9>(out, pk, sk, e);
 }
 
+// ---- many secrets, ONE peer key: the peer's wide comb (x25519_peer.cuh) ---------------------------------------------------
+// The peer's comb, the point it was built for and the key it belongs to live in a buffer of the calling thread that outlives
+// the call (ThreadState::keep, slot KEEP_PEER): PEER_KEEP_WORDS words, laid out as below.  `remembered` is the peer key the
+// comb was built for and a state word (0: nothing yet, 2: remembered and eligible), then the last key refused and a word that
+// says whether there is one: an ineligible peer does not evict the comb of the last eligible one, and a call that repeats it
+// does not pay for its Q again.  `flags` is THIS call's verdict: [0] the comb decides the call,
+// [1] the call builds the comb for a new peer.  Every one-peer kernel of a call reads these words on the device: the host
+// never learns the verdict, and the call does not synchronise.
+constexpr size_t PEER_Q_OFFSET = WB_TBL_WORDS;
+constexpr size_t PEER_REMEMBERED_OFFSET = PEER_Q_OFFSET + PEER_Q_WORDS;          // 8 key words + the state word, 8 + 1 refused
+constexpr size_t PEER_FLAGS_OFFSET = PEER_REMEMBERED_OFFSET + 18;                // 2 words
+constexpr size_t PEER_KEEP_WORDS = PEER_FLAGS_OFFSET + 2;
+constexpr int PEER_ROW_BLOCK = 128;
+
+// One lane: is `pk` the remembered peer?  Then the comb decides iff it was built (state 2).  The last refused key: the ladder.
+// Otherwise, with build_if_new, Q = 8P and the peer's eligibility (x25519_peer_point); an eligible new peer gets Q written for
+// k_x25519_peer_prepare and the remembered state cleared until k_x25519_peer_remember writes the new key down.  Without build_if_new (a call below the
+// ONE_PEER_WIDE size) a new peer runs the ladder: building a comb would cost more than the call takes.
+__global__ void __launch_bounds__(64) k_x25519_peer_check(u32* q_words, u32* remembered, u32* flags, const u32* __restrict__ pk,
+                                                          int build_if_new)
+{
+    if (threadIdx.x != 0) return;
+    u32 u[8], same = remembered[8] != 0, refused = remembered[17] != 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        u[j] = pk[j];
+        same &= remembered[j] == u[j] ? 1u : 0u;
+        refused &= remembered[9 + j] == u[j] ? 1u : 0u;
+    }
+    if (same) {
+        flags[0] = remembered[8] == 2 ? 1u : 0u;
+        flags[1] = 0;
+        return;
+    }
+    if (!build_if_new || refused) {
+        flags[0] = flags[1] = 0;
+        return;
+    }
+    u32 q[3][8];
+    const u32 ok = x25519_peer_point(q, u) ? 1u : 0u;
+    if (ok) {
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) q_words[8 * f + j] = q[f][j];
+        remembered[8] = 0;                                    // the comb is about to change: no call may trust it until remembered
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) remembered[9 + j] = u[j];
+        remembered[17] = 1;
+    }
+    flags[0] = flags[1] = ok;
+}
+
+// the peer's comb: one packed row per thread, the work of k_gen_wide_table for Q instead of B (a call that builds nothing leaves)
+__global__ void __launch_bounds__(PEER_ROW_BLOCK) k_x25519_peer_prepare(u32* wide_peer /*[WB_NT][WB_ROWS][WB_ROW_WORDS]*/,
+                                                                       const u32* __restrict__ q_words, const u32* __restrict__ flags)
+{
+    if (!flags[1]) return;
+    const u32 g = blockIdx.x * PEER_ROW_BLOCK + threadIdx.x;  // table * WB_ROWS + row
+    const int table = (int)(g / WB_ROWS);
+    ge_pa Q;
+    x25519_peer_pa(Q, q_words);
+    u32 rows[3][8];
+    ge_signed_comb_row_of(rows, Q, g % WB_ROWS, (WB_NT - 1 - table) * WB_STEP, WB_TEETH, WB_COLS);
+    uint4* out = reinterpret_cast<uint4*>(wide_peer + (size_t)g * WB_ROW_WORDS);
+#pragma unroll
+    for (int f = 0; f < 3; f++) {
+        out[2 * f] = make_uint4(rows[f][0], rows[f][1], rows[f][2], rows[f][3]);
+        out[2 * f + 1] = make_uint4(rows[f][4], rows[f][5], rows[f][6], rows[f][7]);
+    }
+    out[6] = make_uint4(2, 0, 0, 0);                          // 2Z, as in k_gen_wide_table
+    out[7] = make_uint4(0, 0, 0, 0);
+}
+
+// behind the rows on the stream: the comb now belongs to `pk`
+__global__ void __launch_bounds__(64) k_x25519_peer_remember(u32* remembered, const u32* __restrict__ pk, const u32* __restrict__ flags)
+{
+    if (threadIdx.x != 0 || !flags[1]) return;
+#pragma unroll
+    for (int j = 0; j < 8; j++) remembered[j] = pk[j];
+    remembered[8] = 2;
+}
+
+// the walk: k_x25519_public_fast_mult<true> over the peer's comb with k >> 3; numerator and denominator to the X25519 scratch
+// slots, for the shared inversion behind it
+__global__ void __launch_bounds__(WB_BLOCK, 4) k_x25519_one_peer_mult(ProjScratch scr, void* sk, size_t n, const u32* __restrict__ wide_peer,
+                                                                      const u32* __restrict__ flags)
+{
+    if (!flags[0]) return;                                    // the ladder decides this call
+    __shared__ unsigned short cols[WB_COLS * WB_BLOCK];
+    const size_t i = (size_t)blockIdx.x * WB_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    u32 k[8];
+    load32(k, sk, i);
+    clamp_words(k);
+    store32(sk, i, k);                                        // the reference clamps in the caller's buffer
+    fe num, den;
+    x25519_one_peer_lane(num, den, k, wide_peer, cols + threadIdx.x, WB_BLOCK);
+    soa_store_fe(scr.a, n, i, num);
+    soa_store_fe(scr.z, n, i, den);
+}
+
+// ... and the ladder of the same call, the peer key read with stride 0: k_x25519_ladder for a call that does not walk the comb
+// (wide_ok null: the host knows already, no comb asked for)
+__global__ void __launch_bounds__(XL_BLOCK, C25519_XF_WAVES) k_x25519_ladder_one_peer(u32* X, u32* Z, const void* pk, void* sk, size_t n,
+                                                                                     const u32* __restrict__ wide_ok)
+{
+    if (wide_ok && *wide_ok) return;                          // the comb decides this call
+    const size_t i = (size_t)blockIdx.x * XL_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    u32 u[8], k[8];
+    load32(u, pk, 0);
+    load32(k, sk, i);
+    clamp_words(k);
+    store32(sk, i, k);
+    fe PX, PZ;
+    x25519_ladder_xz<false>(PX, PZ, u, k);
+    soa_store_fe(X, n, i, PX);
+    soa_store_fe(Z, n, i, PZ);
+}
+
+// ... on quads (k_x25519_quad), for the sizes x25519_dev runs there
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_x25519_quad_one_peer(void* out, const void* pk, void* sk, size_t n,
+                                                                                                    const u32* __restrict__ wide_ok)
+{
+    if (wide_ok && *wide_ok) return;
+    const size_t e = (size_t)blockIdx.x * quad::ELEMS_PER_WAVE + (threadIdx.x >> 2);
+    if (e >= n) return;
+    quad::x25519_element<false, true>(out, pk, sk, e);
+}
+
+// the peer key as n records, for the per-wave kernels of a call that asks for no comb
+__global__ void __launch_bounds__(256) k_x25519_peer_broadcast(uint4* dst, const uint4* __restrict__ pk, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * n) dst[i] = pk[i & 1];
+}
+
+// the shared inversion of a call whose ladder (on quads) wrote its results itself: it runs only where the comb decided
+struct FinishX25519IfWide {
+    FinishX25519 fin; const u32* wide_ok;
+    C25519_DEV bool skip() const { return !*wide_ok; }
+    C25519_DEV void emit(size_t e, const fe& zinv) const { fin.emit(e, zinv); }
+};
+
 namespace {
 
 // lanes per X25519 workgroup for a batch of n: the widest shape that still puts a wave on every SIMD the batch can reach
@@ -341,6 +489,120 @@ int curve25519_dh_CalculatePublicKey_dev(void* pk, void* sk, size_t n, void* str
     if (int rc = check_dev_args(n, { pk, sk })) return rc;
     if (n == 0) return 0;
     return x25519_dev(pk, nullptr, sk, n, (hipStream_t)stream);
+}
+
+// ---- many secrets, one peer key ----------------------------------------------------------------
+
+// the smallest call that builds a comb for a NEW peer (tunable ONE_PEER_WIDE; 0 = never).  A call that builds one takes 0.75 ms
+// plus the walk (~1.3 G/s): it loses to the ladder at 2^16 (0.75 against 0.68 ms) and wins at 3 * 2^15 (0.80 against 1.11 ms)
+// and above (tools/one_peer_rate.py, profiles/one_peer_rate.txt).
+constexpr long ONE_PEER_WIDE_DEFAULT = 3L << 15;
+
+// what the calling thread's last one-peer call on this device left behind for c25519_amd_x25519_one_peer_last_wide: where its
+// "the comb decides this call" word lives (null: the call never asked the device)
+struct LastPeer { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
+static thread_local LastPeer tl_last_peer;
+
+// Above the per-wave range a thread that has kept a peer comb asks the device, at any size, whether this call's key is that peer
+// (one lane, 72 bytes); from ONE_PEER_WIDE elements on (the whole of a pipelined *_batch call counts) a new eligible peer gets
+// its comb built first.  The comb walk and the ladder are both enqueued, each kernel leaves at once when the device's verdict
+// is the other's; the ladder is the kernel x25519_dev runs at this size -- on quads, or one lane per element (split from the
+// shared inversion, which both feed).  A call that asks nothing runs the ladder with stride-0 keys, or -- per-wave sizes -- the
+// per-wave kernels on the key broadcast to n records.
+static int x25519_one_peer_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t stream)
+{
+    using c25519_host::ThreadState;
+    const long wide_from = c25519_host::tunable_or(c25519_host::T_ONE_PEER_WIDE, ONE_PEER_WIDE_DEFAULT);   // (read once per call)
+    const size_t whole = std::max(n, c25519_host::batch_shape_hint());
+    const bool quads = x25519_quad_for(n);
+    const bool per_wave = !quads && x25519_coop_for(n);
+    const bool build = wide_from > 0 && whole >= (size_t)wide_from;
+    const bool reuse = !build && wide_from > 0 && !per_wave && tls().has_keep(ThreadState::KEEP_PEER);
+    tl_last_peer = LastPeer();
+    tl_last_peer.ran = true;
+    tl_last_peer.generation = tls().generation;
+    if (!build && !reuse && per_wave) {                      // a few elements: one (or two) waves per element, as x25519_dev runs them
+        void* w = nullptr;
+        c25519_host::WorkLease lease;
+        const void* keys = pk;
+        if (n > 1) {
+            C25519_RC(lease.acquire(&w, 32 * n, stream));
+            k_x25519_peer_broadcast<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)w, (const uint4*)pk, n);
+            C25519_TRY(hipGetLastError());
+            keys = w;
+        }
+        const CallWords cw{};                                 // (records from memory: pk is device memory even in a zero-copy call)
+        if (x25519_two_waves_for(n)) k_x25519_coop2<<<(unsigned)n, 128, 0, stream>>>(out, keys, sk, n, take_done_word(n), cw);
+        else k_x25519_coop<false><<<(unsigned)n, 64, 0, stream>>>(out, keys, sk, n, take_done_word(n), cw);
+        C25519_TRY(hipGetLastError());
+        return n > 1 ? lease.release() : 0;
+    }
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    const bool scratch = build || reuse || !quads;           // (the quads' ladder writes its results itself)
+    C25519_RC(lease.acquire(&w, scratch ? proj_words(n) * sizeof(u32) : 256, stream));
+    const ProjScratch scr = carve_proj((u32*)w, n);
+    const u32* wide_ok = nullptr;
+    c25519_host::KeepLease keep_lease;                        // records the kept buffer's event however this call leaves
+    if (build || reuse) {
+        void* keep = nullptr;
+        bool fresh = false;
+        C25519_RC(keep_lease.acquire(&keep, PEER_KEEP_WORDS * sizeof(u32), stream, &fresh, ThreadState::KEEP_PEER));
+        u32* wide_peer = (u32*)keep;
+        u32* flags = wide_peer + PEER_FLAGS_OFFSET;
+        wide_ok = flags;
+        k_x25519_peer_check<<<1, 64, 0, stream>>>(wide_peer + PEER_Q_OFFSET, wide_peer + PEER_REMEMBERED_OFFSET, flags, (const u32*)pk,
+                                                  build ? 1 : 0);
+        C25519_TRY(hipGetLastError());
+        if (build) {
+            k_x25519_peer_prepare<<<WB_NT * WB_ROWS / PEER_ROW_BLOCK, PEER_ROW_BLOCK, 0, stream>>>(wide_peer, wide_peer + PEER_Q_OFFSET, flags);
+            C25519_TRY(hipGetLastError());
+            k_x25519_peer_remember<<<1, 64, 0, stream>>>(wide_peer + PEER_REMEMBERED_OFFSET, (const u32*)pk, flags);
+            C25519_TRY(hipGetLastError());
+        }
+        k_x25519_one_peer_mult<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(scr, sk, n, wide_peer, flags);
+        C25519_TRY(hipGetLastError());
+        tl_last_peer.wide_ok = wide_ok; tl_last_peer.stream = stream;
+        (void)hipGetDevice(&tl_last_peer.device);
+    }
+    if (quads) {
+        k_x25519_quad_one_peer<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(out, pk, sk, n, wide_ok);
+        C25519_TRY(hipGetLastError());
+        if (wide_ok) C25519_RC(launch_invert(scr, n, FinishX25519IfWide{ FinishX25519{ scr.a, out, n }, wide_ok }, stream));
+    } else {
+        k_x25519_ladder_one_peer<<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n, wide_ok);
+        C25519_TRY(hipGetLastError());
+        C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
+    }
+    C25519_RC(keep_lease.release());
+    return lease.release();
+}
+
+int curve25519_dh_CreateSharedKey_one_peer_dev(void* shared, const void* pk, void* sk, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!shared || !pk || !sk) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { shared, pk, sk })) return rc;
+    if (n == 0) return 0;
+    return x25519_one_peer_dev(shared, pk, sk, n, (hipStream_t)stream);
+}
+
+// test / accounting hook: did the calling thread's last one-peer call on this device walk the peer's comb (1), or the ladder (0: the
+// call did not ask -- per-wave size, no kept comb below ONE_PEER_WIDE, ONE_PEER_WIDE = 0 -- or the device said no: another peer
+// than the remembered one below ONE_PEER_WIDE, a peer off the curve or u = -1)?  -1: no such call.  Synchronises with that call's
+// stream.  (A *_batch call of several pieces reports its last piece.)
+long c25519_amd_x25519_one_peer_last_wide(void)
+{
+    C25519_API_CALL_OR(-1);
+    const LastPeer& lp = tl_last_peer;
+    if (!lp.ran || lp.generation != tls().generation) return -1;    // (c25519_amd_thread_release() / a device switch since)
+    if (!lp.wide_ok) return 0;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != lp.device) return -1;
+    if (hipStreamSynchronize(lp.stream) != hipSuccess) return -1;
+    u32 v = 0;
+    if (hipMemcpy(&v, lp.wide_ok, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return v ? 1 : 0;
 }
 
 }  // extern "C"

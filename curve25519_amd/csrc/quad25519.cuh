@@ -113,12 +113,13 @@ C25519_DEV void ladder_step(fe& own, const fe& x1, u32 eq, const Roles& R)
 // The first doubling (Q = 2P, :125), the three doublings for the clamped-away low bits and the inversion have no
 // four-way structure worth an exchange: every lane runs them on the same values (the inversion is 12 % of the element's
 // chain -- Montgomery's trick would share it between the 16 elements of the wave but not shorten the chain).
-template <bool BASE9>
+// ONE_PK: every element against the same peer key, pk[0] (curve25519_dh_CreateSharedKey_one_peer's ladder)
+template <bool BASE9, bool ONE_PK = false>
 C25519_DEV void x25519_element(void* out, const void* pk, void* sk, size_t e)
 {
     const Roles R = roles();
     u32 u[8] = { 9, 0, 0, 0, 0, 0, 0, 0 }, k[8];
-    if (!BASE9) load32(u, pk, e);
+    if (!BASE9) load32(u, pk, ONE_PK ? 0 : e);
     load32(k, sk, e);
     clamp_words(k);
     if (R.is0) store32(sk, e, k);                      // the reference clamps in the caller's buffer

@@ -48,7 +48,10 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * ladder on two waves per element, default 512; 0 = never), QUAD_MIN / QUAD_MAX (calls of more than QUAD_MIN and at most QUAD_MAX
  * elements run FOUR LANES per element -- X25519: the whole operation, defaults 3584 / 32768; ed25519_VerifySignature_*: scalars
  * and point tables side by side, the walk on quads, defaults 1024 / 32768; key pairs, signatures, CalculatePublicKey_fast and the
- * one-key ed25519_Verify_Check_* with a comb: the whole operation in one launch, defaults 1024 / 16384; QUAD_MAX = 0: never).
+ * one-key ed25519_Verify_Check_* with a comb: the whole operation in one launch, defaults 1024 / 16384; QUAD_MAX = 0: never),
+ * ONE_PEER_WIDE (curve25519_dh_CreateSharedKey_one_peer_*: the smallest batch that BUILDS a wide comb for a new peer key; a call
+ * of more than 3584 elements with the peer the calling thread's last comb was built for walks that comb whatever its size;
+ * default 98304; 0 = never).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -84,6 +87,22 @@ int c25519_amd_host_unregister(void *p);
 int curve25519_dh_CreateSharedKey_batch(unsigned char *shared, const unsigned char *pk,
                                         unsigned char *sk, size_t n);
 int curve25519_dh_CreateSharedKey_dev(void *shared, const void *pk, void *sk, size_t n, void *stream);
+
+/* n x curve25519_dh_CreateSharedKey with the SAME 32-byte peer key pk for every element (sealed-box / HPKE-style encryption of
+ * many records to one recipient, a server re-keying many ephemeral secrets against one static key); sk is clamped in place.
+ * Byte-identical to curve25519_dh_CreateSharedKey_* with pk repeated n times, for every pk.  From ONE_PEER_WIDE elements per
+ * call (tunable, see above) a peer on the curve gets a wide fixed-base comb built for 8 * pk (0.6 ms; kept in 2 MiB of device
+ * memory per calling thread until the thread exits or calls c25519_amd_thread_release()), and the call walks it instead of
+ * the Montgomery ladder; a later call of more than the per-wave sizes (3584 elements) with the same pk walks the kept comb
+ * whatever its size.  Other calls, and peers on the twist (or u = -1), run the ladder.  The _dev form does not synchronise: pk is read on
+ * the device. */
+int curve25519_dh_CreateSharedKey_one_peer_batch(unsigned char *shared, const unsigned char *pk /* 32 bytes */,
+                                                 unsigned char *sk, size_t n);
+int curve25519_dh_CreateSharedKey_one_peer_dev(void *shared, const void *pk /* 32 bytes, device */, void *sk, size_t n,
+                                               void *stream);
+/* did the calling thread's last curve25519_dh_CreateSharedKey_one_peer_* call on this device walk the peer's comb (1) or the
+ * ladder (0)?  -1: no such call.  Synchronises with that call's stream.  (A *_batch call of several pieces reports its last piece.) */
+long c25519_amd_x25519_one_peer_last_wide(void);
 
 /* n x curve25519_dh_CalculatePublicKey (reference :34): ladder on the base point u = 9 */
 int curve25519_dh_CalculatePublicKey_batch(unsigned char *pk, unsigned char *sk, size_t n);
