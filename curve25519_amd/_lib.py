@@ -63,6 +63,7 @@ SIGNATURES = {
     "c25519_amd_quad_limb_selftest": [_vp, _vp, _sz, C.c_int],
     "c25519_amd_wave_limb_selftest": [_vp, _vp, _sz, C.c_int],
     "c25519_amd_verify_point_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "c25519_amd_batch_invert_selftest_dev": [_vp, _vp, _sz, C.c_int, _vp],
     "c25519_amd_device_count": [],
     "c25519_amd_set_device": [C.c_int],
     "c25519_amd_version": [],

@@ -245,6 +245,18 @@ int c25519_amd_fe_limb_selftest(unsigned* out, const unsigned* in, size_t n, int
 int c25519_amd_quad_limb_selftest(unsigned* out, const unsigned* in, size_t n, int op) { return limb_selftest(out, in, n, op, 1, 4); }
 int c25519_amd_wave_limb_selftest(unsigned* out, const unsigned* in, size_t n, int op) { return limb_selftest(out, in, n, op, 2, 7); }
 
+// the shared inversion alone (k_batch_invert with FinishInverse): ONE launch over device pointers, since the slot map depends on n
+int c25519_amd_batch_invert_selftest_dev(void* out, const void* in, size_t n, int k, void* stream)
+{
+    C25519_API_CALL();
+    if (!out || !in) return bad_arg("null pointer");
+    if (k > INV_MAX_K) return bad_arg("batch inversion self-test: k > 16");
+    if (int rc = check_dev_args(n, { out, in })) return rc;
+    if (n == 0) return 0;
+    const ProjScratch scr{ nullptr, nullptr, const_cast<u32*>(static_cast<const u32*>(in)), nullptr };
+    return launch_invert_k(scr, n, k <= 0 ? inversion_k(n) : k, FinishInverse{ static_cast<u32*>(out) }, (hipStream_t)stream);
+}
+
 int c25519_amd_sc_selftest(unsigned char* out, const unsigned char* a, const unsigned char* b, size_t n, int op)
 {
     if (!out || !a || !b) return bad_arg("null pointer");

@@ -27,6 +27,7 @@
 #include "coop25519.cuh"
 #include "coop_ops.cuh"
 #include "quad25519.cuh"
+#include "batch_invert.cuh"
 
 #include "../../include/curve25519_amd.h"
 #include "../../include/curve25519_dh.h"
@@ -60,31 +61,7 @@ struct ProjScratch {            // projective result + prefix products of the ba
 #endif
 constexpr int ED_BLOCK = C25519_ED_BLOCK;
 
-C25519_DEV void lds_put_fe(u32* buf, int stride, int idx, const fe& f)
-{
-#pragma unroll
-    for (int w = 0; w < 10; w++) buf[w * stride + idx] = f.v[w];
-}
-C25519_DEV void lds_get_fe(fe& f, const u32* buf, int stride, int idx)
-{
-#pragma unroll
-    for (int w = 0; w < 10; w++) f.v[w] = buf[w * stride + idx];
-}
-
-// z <- 1 where z == 0 (mod p), returns all-ones in that case: a zero takes no part in a shared inversion and its
-// "inverse" is forced to 0 afterwards, which is what the reference's z^(p-2) gives (curve25519_dh.c:148)
-C25519_DEV u32 fe_zero_to_one(fe& z)
-{
-    u32 w[8], nz = 0;
-    fe_to_words(w, z);
-#pragma unroll
-    for (int q = 0; q < 8; q++) nz |= w[q];
-    const u32 is_zero = nz ? 0u : 0xffffffffu;
-    fe one;
-    fe_set_u32(one, 1);
-    fe_select(z, is_zero, one, z);
-    return is_zero;
-}
+// (lds_put_fe / lds_get_fe, fe_zero_to_one: batch_invert.cuh)
 
 // a projective Edwards point into the scratch between the kernels of a pass
 C25519_DEV void store_proj(const ProjScratch& scr, size_t n, size_t i, const ge_ext& S)
@@ -169,12 +146,7 @@ struct FinishVerify {                        // verdict = (enc(T) == enc(R) byte
     }
 };
 
-#ifndef C25519_INV_QUAD
-#define C25519_INV_QUAD 1            // A/B switch: 0 = every lane of k_batch_invert inverts its own product (profiles/r06_ab_inv_quad.txt)
-#endif
-constexpr int INV_BLOCK = 64;
-constexpr int INV_MAX_K = 16;
-
+// (INV_BLOCK, INV_MAX_K, C25519_INV_QUAD: batch_invert.cuh; the lane's work: batch_invert_lane.inc)
 // K is a compile-time constant and the loops are unrolled: a lane's K elements live in registers (a lone wave per SIMD has
 // the whole register file: 64-thread workgroups, no occupancy to protect), so the loads of all K elements are issued up
 // front instead of one dependent round trip per element and per pass.  The K - 1 prefix products a lane needs again on
@@ -186,66 +158,8 @@ __global__ void __launch_bounds__(INV_BLOCK) __attribute__((amdgpu_waves_per_eu(
 {
     (void)prefix;
     if (fin.skip()) return;                                 // (uniform: a word of the call's scratch)
-    constexpr bool PREFIX_IN_LDS = K > 14;
-    __shared__ u32 pre_lds[PREFIX_IN_LDS ? (K - 1) * 10 * INV_BLOCK : 1];
-    const size_t j = (size_t)blockIdx.x * INV_BLOCK + threadIdx.x;
-    const bool live = j < m;                                // (a lane past the end stays: its quad shares the inversion below)
-    fe z[K], pre[PREFIX_IN_LDS ? 1 : K];
-    u32 zero_mask = 0;
-#pragma unroll
-    for (int t = 0; t < K; t++) {
-        const size_t e = j + (size_t)t * m;
-        if (live && e < n) soa_load_fe(z[t], Z, n, e);
-        else fe_set_u32(z[t], 1);                           // past the end: a factor of one
-    }
-    fe acc;
-#pragma unroll
-    for (int t = 0; t < K; t++) {
-        zero_mask |= (fe_zero_to_one(z[t]) & 1u) << t;      // z == 0 (mod p) takes no part in the product
-        if (t == 0) acc = z[0];
-        else fe_mul(acc, acc, z[t]);
-        if (t < K - 1) {
-            if (PREFIX_IN_LDS) lds_put_fe(pre_lds + t * 10 * INV_BLOCK, INV_BLOCK, threadIdx.x, acc);
-            else pre[t] = acc;
-        }
-    }
-    // ONE inversion per QUAD of lanes (4 K elements): the pairs' products, the quad's product T, 1 / T by the four lanes together
-    // (fe_invert_quad: the division steps' three pairs on three lanes, ~7 700 instructions instead of one lane's ~13 700), then
-    // each lane's own 1 / acc = (1 / T) * (the other pair's product) * (its partner's product)
-    fe inv;
-#if C25519_INV_QUAD
-    {
-        fe partner, pair, other_pair, total;
-        quad::fe_qperm<1, 0, 3, 2>(partner, acc);
-        fe_mul(pair, acc, partner);
-        quad::fe_qperm<2, 3, 0, 1>(other_pair, pair);
-        fe_mul(total, pair, other_pair);
-        fe_invert_quad(inv, total);
-        fe_mul(inv, inv, other_pair);
-        fe_mul(inv, inv, partner);
-    }
-#else
-    fe_invert(inv, acc);
-#endif
-#pragma unroll
-    for (int t = K - 1; t >= 0; t--) {
-        const size_t e = j + (size_t)t * m;
-        fe zi;
-        if (t > 0) {
-            fe p;
-            if (PREFIX_IN_LDS) lds_get_fe(p, pre_lds + (t - 1) * 10 * INV_BLOCK, INV_BLOCK, threadIdx.x);
-            else p = pre[t - 1];
-            fe_mul(zi, inv, p);
-            fe_mul(inv, inv, z[t]);
-        } else {
-            zi = inv;
-        }
-        const u32 was_zero = ((zero_mask >> t) & 1u) ? 0xffffffffu : 0u;
-        fe zero;
-        fe_set_u32(zero, 0);
-        fe_select(zi, was_zero, zero, zi);
-        if (live && e < n) fin.emit(e, zi);
-    }
+    __shared__ u32 pre_lds[K > 14 ? (K - 1) * 10 * INV_BLOCK : 1];
+#include "batch_invert_lane.inc"
 }
 
 // ================================================================================================
@@ -298,11 +212,12 @@ inline int inversion_k(size_t n)
     return (int)k;
 }
 
+// K elements per lane, rounded down to an instantiated group size (inversion_group): the product path passes inversion_k(n), the
+// self-test hook (c25519_amd_batch_invert_selftest_dev) any size
 template <typename Fin>
-int launch_invert(const ProjScratch& scr, size_t n, const Fin& fin, hipStream_t stream)
+int launch_invert_k(const ProjScratch& scr, size_t n, int k, const Fin& fin, hipStream_t stream)
 {
-    int K = inversion_k(n);
-    K = K >= 16 ? 16 : K >= 14 ? 14 : K >= 12 ? 12 : K >= 8 ? 8 : K >= 4 ? 4 : K >= 2 ? 2 : 1;           // the instantiated group sizes
+    const int K = inversion_group(k);
     const size_t m = (n + K - 1) / K;
     const unsigned grid = grid_for(m, INV_BLOCK);
     switch (K) {
@@ -316,6 +231,12 @@ int launch_invert(const ProjScratch& scr, size_t n, const Fin& fin, hipStream_t 
     }
     C25519_TRY(hipGetLastError());
     return 0;
+}
+
+template <typename Fin>
+int launch_invert(const ProjScratch& scr, size_t n, const Fin& fin, hipStream_t stream)
+{
+    return launch_invert_k(scr, n, inversion_k(n), fin, stream);
 }
 
 // a call of a few elements -- the reference's single-call prototypes are a batch of one -- runs ONE operation per wave

@@ -253,6 +253,13 @@ int c25519_amd_fe_limb_selftest(unsigned *out, const unsigned *in, size_t n, int
 int c25519_amd_quad_limb_selftest(unsigned *out, const unsigned *in, size_t n, int op);
 int c25519_amd_wave_limb_selftest(unsigned *out, const unsigned *in, size_t n, int op);
 
+/* the shared inversion of the batch kernels (k_batch_invert, csrc/batch_invert_lane.inc: Montgomery's trick over k elements per
+ * lane, one inversion per quad of lanes) on its own, as one launch on `stream` (device pointers): in holds n field elements as ten 32-bit limbs each in the
+ * struct-of-arrays layout of the kernels' scratch (limb w of element e at word w*n + e), out gets n x 32 bytes, the canonical
+ * little-endian 1/z of each (0 for z = 0 mod p).  k <= 0: the group size the product kernels would take for n; 1..16 round down
+ * to an instantiated size (1, 2, 4, 8, 12, 14, 16) as the INV_K knob does. */
+int c25519_amd_batch_invert_selftest_dev(void *out, const void *in, size_t n, int k, void *stream);
+
 /* device scalar arithmetic mod L (reference source/curve25519_order.c, unit checks test/curve25519_selftest.c:624-714):
  * a is n x 64 bytes (512-bit little-endian), b n x 32 bytes, out n x 32 bytes.
  *   op 0 canonical(a mod L)   1 raw a mod L            2 canonical(a[0..31] mod L)   3 raw a[0..31]*b

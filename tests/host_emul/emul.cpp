@@ -10,6 +10,7 @@
 #include "verify_fast.cuh"
 #include "coop_ops.cuh"
 #include "quad25519.cuh"
+#include "batch_invert.cuh"
 
 #include <mutex>
 #include <thread>
@@ -637,6 +638,45 @@ void emul_quad_x25519(unsigned char* out, const unsigned char* pk, unsigned char
             if (pk) quad::x25519_element<false>(out, pk, sk, e);
             else quad::x25519_element<true>(out, pk, sk, e);
         });
+}
+
+}  // extern "C"
+
+// ---- the shared inversion: k_batch_invert<FinishInverse, K> is the LDS prefix buffer and csrc/batch_invert_lane.inc, which is
+// included here as the body of a lane; every workgroup is a wave of 64 lock-step lanes, so the quads' exchange goes through the
+// quad_perm model.  in: n field elements as limbs, limb w of element e at w * n + e; out: n x 8 canonical words of 1 / z.
+// k: elements per lane, rounded down to an instantiated size as c25519_amd_batch_invert_selftest_dev does.  Returns the size used.
+template <typename Fin, int K>
+static void batch_invert_lane(const u32* Z, u32* pre_lds, size_t n, size_t m, Fin fin, unsigned block)
+{
+    const emul_dim3 blockIdx = { block, 0, 0 };               // (valu_model.h's is always 0)
+#include "batch_invert_lane.inc"
+}
+
+template <int K>
+static void emul_batch_invert_k(u32* out, const u32* in, size_t n)
+{
+    const size_t m = (n + K - 1) / K;
+    std::vector<u32> pre_lds(K > 14 ? (K - 1) * 10 * INV_BLOCK : 1);
+    for (unsigned block = 0; (size_t)block * INV_BLOCK < m; block++)
+        emul_coop::run_block(INV_BLOCK, [&] { batch_invert_lane<FinishInverse, K>(in, pre_lds.data(), n, m, FinishInverse{ out }, block); });
+}
+extern "C" {
+
+int emul_batch_invert(unsigned* out, const unsigned* in, size_t n, int k)
+{
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    const int K = inversion_group(k);
+    switch (K) {
+    case 16: emul_batch_invert_k<16>(out, in, n); break;
+    case 14: emul_batch_invert_k<14>(out, in, n); break;
+    case 12: emul_batch_invert_k<12>(out, in, n); break;
+    case 8:  emul_batch_invert_k<8>(out, in, n); break;
+    case 4:  emul_batch_invert_k<4>(out, in, n); break;
+    case 2:  emul_batch_invert_k<2>(out, in, n); break;
+    default: emul_batch_invert_k<1>(out, in, n); break;
+    }
+    return K;
 }
 
 // the fixed-base operations on quads (k_ed25519_keypair_quad / k_ed25519_sign_quad / k_x25519_public_fast_quad): the kernels are the
