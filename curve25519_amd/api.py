@@ -165,6 +165,42 @@ def ed25519_Verify_Check(ctx, sig, msg):
     return ok
 
 
+def _ctx_index(ctxs, idx, n):
+    ctxs = _np(ctxs, 2080, "ctxs") if np.size(ctxs) else np.zeros((0, 2080), np.uint8)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    if idx.size != n:
+        raise ValueError("one context index per signature")
+    return ctxs, idx
+
+
+def ed25519_Verify_Check_indexed(ctxs, idx, sig, msg):
+    """Many keys in one call: uint8[n_ctx, 2080] contexts (Verify_Init's), uint32[n] indices, n (signature, message) pairs ->
+    int32[n], element i checked against context idx[i] as ed25519_Verify_Check would.  An index >= n_ctx raises EngineError."""
+    sig = _np(sig, 64, "sig")
+    n = sig.shape[0]
+    ctxs, idx = _ctx_index(ctxs, idx, n)
+    msg, msg_size = _msgs(msg, n)
+    ok = np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_Verify_Check_indexed_batch(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig), _ptr(msg),
+                                                               msg_size, n), "ed25519_Verify_Check_indexed_batch")
+    return ok
+
+
+def ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages):
+    """ed25519_Verify_Check_indexed with per-element message lengths (`messages`: sequence of bytes-like)."""
+    sig = _np(sig, 64, "sig")
+    n = sig.shape[0]
+    ctxs, idx = _ctx_index(ctxs, idx, n)
+    if len(messages) != n:
+        raise ValueError("one message per signature")
+    flat, offsets = _ragged(messages)
+    ok = np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_Verify_Check_indexed_ragged_batch(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig),
+                                                                      _ptr(flat), _ptr(offsets), n),
+               "ed25519_Verify_Check_indexed_ragged_batch")
+    return ok
+
+
 def base_folding8_table():
     """(256, 3, 32) uint8: the device-generated 8-fold base table in the reference's PA_POINT row order."""
     out = np.empty((256, 3, 32), np.uint8)
@@ -251,6 +287,18 @@ def ed25519_SignMessage_dev(sig, priv, msg):
     args = (_check(sig, 64, "sig", n, device=d), _check(priv, 64, "priv"), _check(msg, None, "msg", n, device=d))
     with _on(priv) as st:
         _lib.check(_lib.load().ed25519_SignMessage_dev(*args, msg.shape[1], n, st), "ed25519_SignMessage_dev")
+
+
+def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):
+    """Device form of ed25519_Verify_Check_indexed: ctxs uint8[n_ctx, 2080], idx int32[n, 1] (read as uint32), verdict int32[n, 1].
+    An index >= n_ctx gives verdict 0 (nothing is checked on the host)."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(ctxs, 2080, "ctxs", device=d))
+    args += (ctxs.shape[0], _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
+             _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_Verify_Check_indexed_dev(*args, msg.shape[1], n, st), "ed25519_Verify_Check_indexed_dev")
 
 
 def ed25519_VerifySignature_dev(verdict, sig, pk, msg):

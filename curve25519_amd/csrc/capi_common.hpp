@@ -235,6 +235,8 @@ struct ThreadState {
     void* vctx = nullptr;                  // the 2080-byte context of this thread's last ed25519_Verify_Check_batch (nothing else writes it)
     unsigned char vctx_host[2080] = {};    // ... and the bytes that were uploaded into it
     bool vctx_valid = false;
+    void* vctxs = nullptr;                 // the n_ctx x 2080 bytes of this thread's last ed25519_Verify_Check_indexed_*batch (grow-only)
+    size_t vctxs_cap = 0;
     void* bctx = nullptr;                  // the same for the 192-byte blinding context of this thread's last blinded *_batch call
     unsigned char bctx_host[192] = {};
     bool bctx_valid = false;
@@ -460,6 +462,8 @@ struct ThreadState {
         done_offered = done_taken = false;
         if (vctx) { (void)hipMemset(vctx, 0, 2080); (void)hipFree(vctx); vctx = nullptr; }
         vctx_valid = false;
+        if (vctxs) { (void)hipMemset(vctxs, 0, vctxs_cap); (void)hipFree(vctxs); vctxs = nullptr; }
+        vctxs_cap = 0;
         if (bctx) { (void)hipMemset(bctx, 0, 192); (void)hipFree(bctx); bctx = nullptr; }
         memset(bctx_host, 0, sizeof bctx_host);
         bctx_valid = false;

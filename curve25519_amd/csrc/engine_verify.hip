@@ -2,6 +2,7 @@
 // reference order, the two-phase calls with one key (shared table, two wide combs) -- kernels and *_dev entry points
 // (one of the engine's four translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
+#include "verify_ctx.cuh"
 
 // ed25519_Verify_Init (ed25519_verify.c:179-232): decompress -A (inverted parity :192-195, no validation) and
 // fill the key's 16-row 4-fold table.  `tables` holds n tables of Tbl's format, `stride_words` apart.
@@ -487,6 +488,56 @@ k_ed25519_verify_check_wide_quad(int* verdict, const void* sig, const u32* __res
                                     cols + WB_COLS * 64 + threadIdx.x, 64);
 }
 
+// ---- many contexts in one call: element i against context ctx_index[i] (verify_ctx.cuh) ------------------------------------------
+// Per lane, as k_ed25519_verify_check_shared with the element's own context: the 8-fold base table staged in LDS, the 16 rows of the
+// context read from global memory at each lookup (QTableCanon: one 128-byte row, 2080k + 32 + 128r bytes into the call's contexts,
+// so three of every four contexts' rows straddle two lines; C25519_INDEXED_REPACK = 1 reads an aligned copy of them instead).
+__global__ void __launch_bounds__(ED_BLOCK, 2) k_ed25519_verify_check_indexed(ProjScratch scr, const void* sig, const u32* __restrict__ ctxs,
+                                                                               size_t n_ctx, const u32* __restrict__ ctx_index, Msgs msgs,
+                                                                               size_t n, const u32* __restrict__ g_tbl, const u32* __restrict__ rows)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds_tbl[PA_WORDS * 256];
+    lds_stage_words(lds_tbl, g_tbl + REF_TBL_OFFSET, REF_TBL_WORDS);
+    const size_t i = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32* ctx = indexed_ctx(ctxs, n_ctx, ctx_index, i);
+#if C25519_INDEXED_REPACK
+    const QTableCanon tbl{ const_cast<u32*>(rows) + (ctx ? (size_t)ctx_index[i] * QTABLE_CANON_WORDS : 0) };
+#else
+    (void)rows;
+    const QTableCanon tbl{ const_cast<u32*>(ctx) + 8 };
+#endif
+    ge_ext T;
+    verify_ctx_point(T, ctx, tbl, sig, msgs, i, lds_tbl);
+    store_proj(scr, n, i, T);
+}
+
+#if C25519_INDEXED_REPACK
+// the rows of the call's contexts, 2048 bytes per context, into `rows` (128-byte aligned): one 16-byte word per thread
+__global__ void __launch_bounds__(256) k_ed25519_verify_ctx_repack(uint4* rows, const u32* __restrict__ ctxs, size_t n_ctx)
+{
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_ctx * (QTABLE_CANON_WORDS / 4)) return;
+    const size_t k = g / (QTABLE_CANON_WORDS / 4), q = g % (QTABLE_CANON_WORDS / 4);
+    rows[g] = reinterpret_cast<const uint4*>(ctxs + k * VCTX_WORDS + 8)[q];
+}
+#endif
+
+// ... and for a call of a few pairs, one pair per wave (k_ed25519_verify_check_coop with the element's context)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4)))
+k_ed25519_verify_check_indexed_coop(int* verdict, const void* sig, const u32* __restrict__ ctxs, size_t n_ctx,
+                                    const u32* __restrict__ ctx_index, Msgs msgs, size_t n, const u32* __restrict__ g_tbl, DoneWord done)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[coop::Q_LDS_WORDS];
+    if (blockIdx.x >= n) return;
+    const u32* ctx = indexed_ctx(ctxs, n_ctx, ctx_index, blockIdx.x);
+    if (ctx)
+        coop::verify_check_one(lds, coop::make_lane(threadIdx.x), verdict, sig, ctx, msgs, blockIdx.x, g_tbl + REF_TBL_OFFSET);
+    else if (threadIdx.x == 0)
+        verdict[blockIdx.x] = 0;
+    if (threadIdx.x == 0) signal_done(done);
+}
+
 namespace {
 
 // scratch of one verification pass: per-lane tables (the larger of the two paths' formats: they never live at the same
@@ -729,6 +780,57 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
     C25519_RC(keep_lease.release());
     return lease.release();
+}
+
+// n x ed25519_Verify_Check(ctxs + 2080 * ctx_index[i], pair i): up to COOP_MAX pairs (default 1024) one per wave, above that one per
+// lane and the shared inversion.  An index >= n_ctx gives verdict 0 (the device cannot refuse the call without a synchronise).
+static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig, Msgs msgs,
+                                    size_t n, hipStream_t stream)
+{
+    if (int rc = check_dev_args(n, { verdict, ctxs, ctx_index, sig })) return rc;
+    if (n == 0) return 0;
+    if (n_ctx == 0) return bad_arg("no contexts");
+    const u32* tbl = nullptr;
+    C25519_RC(base_tables(&tbl, nullptr));
+    if (coop_for(n, 1024)) {
+        k_ed25519_verify_check_indexed_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctxs, n_ctx,
+                                                                            (const u32*)ctx_index, msgs, n, tbl, take_done_word(n));
+        C25519_TRY(hipGetLastError());
+        return 0;
+    }
+    const size_t row_words = C25519_INDEXED_REPACK ? n_ctx * QTABLE_CANON_WORDS : 0;
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, (row_words + proj_words(n)) * sizeof(u32), stream));
+    u32* rows = (u32*)w;                                    // first in the slab (hipMalloc: 256-byte aligned): whole 128-byte rows
+    const ProjScratch scr = carve_proj(rows + row_words, n);
+#if C25519_INDEXED_REPACK
+    k_ed25519_verify_ctx_repack<<<grid_for(n_ctx * (QTABLE_CANON_WORDS / 4), 256), 256, 0, stream>>>((uint4*)rows, (const u32*)ctxs, n_ctx);
+    C25519_TRY(hipGetLastError());
+#endif
+    k_ed25519_verify_check_indexed<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(scr, sig, (const u32*)ctxs, n_ctx, (const u32*)ctx_index,
+                                                                                  msgs, n, tbl, rows);
+    C25519_TRY(hipGetLastError());
+    C25519_RC(launch_invert(scr, n, FinishVerifyIndexed{ scr.a, scr.b, sig, (int*)verdict, n, (const u32*)ctx_index, n_ctx }, stream));
+    return lease.release();
+}
+
+int ed25519_Verify_Check_indexed_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig,
+                                     const void* msg, size_t msg_size, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n,
+                                    (hipStream_t)stream);
+}
+
+int ed25519_Verify_Check_indexed_ragged_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig,
+                                            const void* msgs, const uint64_t* offsets, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets },
+                                    n, (hipStream_t)stream);
 }
 
 // test / accounting hook: did the calling thread's last ed25519_Verify_Check_* call on this device walk the two wide combs (1), or

@@ -196,6 +196,24 @@ int ed25519_Verify_Check_batch(int *verdict, const void *ctx, const unsigned cha
                                const unsigned char *msg, size_t msg_size, size_t n);
 int ed25519_Verify_Check_dev(void *verdict, const void *ctx, const void *sig, const void *msg,
                              size_t msg_size, size_t n, void *stream);
+/* n x ed25519_Verify_Check(ctxs + 2080 * ctx_index[i], sig_i, msg_i): MANY contexts in one call, a mixed stream of
+ * (context, signature, message) triples in any order.  ctxs holds n_ctx records of 2080 bytes (Verify_Init's layout, read as
+ * they are, like the reference: element i's verdict is what ed25519_Verify_Check_* gives for its context, tampered or not),
+ * ctx_index is n x uint32.  The index is public data: its gather is not constant-time.
+ *   n == 0 returns 0; a null pointer, or n_ctx == 0 with n > 0, is an argument error.
+ *   *_batch checks every index on the host: one >= n_ctx refuses the call before any work, verdict untouched.
+ *   *_dev cannot check without a synchronise: an index >= n_ctx gives verdict 0 and nothing outside ctxs is read.
+ *   *_batch uploads the contexts once per call into a device buffer of the calling thread (zeroed before it is freed by
+ *   c25519_amd_thread_release() or a larger call).  Up to COOP_MAX pairs (default 1024) run one per wave, larger calls one per
+ *   lane over the contexts' rows in place (profiles/indexed_check_rate.txt). */
+int ed25519_Verify_Check_indexed_batch(int *verdict, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                       const unsigned char *sig, const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_Verify_Check_indexed_dev(void *verdict, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                     const void *sig, const void *msg, size_t msg_size, size_t n, void *stream);
+int ed25519_Verify_Check_indexed_ragged_batch(int *verdict, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                              const unsigned char *sig, const unsigned char *msgs, const uint64_t *offsets, size_t n);
+int ed25519_Verify_Check_indexed_ragged_dev(void *verdict, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                            const void *sig, const void *msgs, const uint64_t *offsets, size_t n, void *stream);
 
 /* Multi-GPU (BASELINE.json north_star: "batches shard embarrassingly across the 8 GPUs of one node
  * with a single RCCL gather over xGMI") ------------------------------------------------------------------------------
