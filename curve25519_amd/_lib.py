@@ -15,6 +15,11 @@ SIGNATURES = {
     "curve25519_dh_CreateSharedKey_one_peer_batch": [_vp, _vp, _vp, _sz],
     "curve25519_dh_CreateSharedKey_one_peer_dev": [_vp, _vp, _vp, _sz, _vp],
     "c25519_amd_x25519_one_peer_last_wide": [],
+    "curve25519_dh_Peer_Init_batch": [_vp, _vp, _sz],
+    "curve25519_dh_Peer_Init_dev": [_vp, _vp, _sz, _vp],
+    "curve25519_dh_CreateSharedKey_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _sz],
+    "curve25519_dh_CreateSharedKey_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _vp],
+    "c25519_amd_x25519_indexed_last_ladder_elements": [],
     "curve25519_dh_CalculatePublicKey_batch": [_vp, _vp, _sz],
     "curve25519_dh_CalculatePublicKey_dev": [_vp, _vp, _sz, _vp],
     "curve25519_dh_CalculatePublicKey_fast_batch": [_vp, _vp, _sz],
@@ -90,6 +95,7 @@ _RESTYPE = {
     "c25519_amd_verify_last_slow_elements": C.c_long,
     "c25519_amd_verify_check_last_wide": C.c_long,
     "c25519_amd_x25519_one_peer_last_wide": C.c_long,
+    "c25519_amd_x25519_indexed_last_ladder_elements": C.c_long,
     "c25519_amd_tunable_get": C.c_long,
     "c25519_amd_version": C.c_char_p,
     "c25519_amd_last_error": C.c_char_p,

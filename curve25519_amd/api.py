@@ -64,6 +64,37 @@ def curve25519_dh_CreateSharedKey_one_peer(pk, sk):
     return out, sk
 
 
+PEER_CTX_SIZE = 1600
+
+
+def curve25519_dh_Peer_Init(pk):
+    """n x curve25519_dh_Peer_Init: peer contexts, uint8[n, 1600] (pk || eligibility || 16 affine rows of 8 * pk's point)."""
+    pk = _np(pk, 32, "pk")
+    ctx = np.empty((pk.shape[0], PEER_CTX_SIZE), np.uint8)
+    _lib.check(_lib.load().curve25519_dh_Peer_Init_batch(_ptr(ctx), _ptr(pk), pk.shape[0]), "curve25519_dh_Peer_Init_batch")
+    return ctx
+
+
+def curve25519_dh_CreateSharedKey_indexed(ctxs, idx, sk):
+    """Many peers in one call: uint8[n_ctx, 1600] contexts (Peer_Init's), uint32[n] indices, n secrets -> (shared, clamped_sk),
+    element i against the key of context idx[i] as curve25519_dh_CreateSharedKey would.  An index >= n_ctx raises EngineError."""
+    sk = np.array(_np(sk, 32, "sk"), copy=True)
+    n = sk.shape[0]
+    ctxs = _np(ctxs, PEER_CTX_SIZE, "ctxs") if np.size(ctxs) else np.zeros((0, PEER_CTX_SIZE), np.uint8)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    if idx.size != n:
+        raise ValueError("one context index per secret")
+    out = np.empty_like(sk)
+    _lib.check(_lib.load().curve25519_dh_CreateSharedKey_indexed_batch(_ptr(out), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sk), n),
+               "curve25519_dh_CreateSharedKey_indexed_batch")
+    return out, sk
+
+
+def x25519_indexed_last_ladder_elements():
+    """elements of the calling thread's last CreateSharedKey_indexed call that ran the ladder (-1: no such call); synchronises"""
+    return int(_lib.load().c25519_amd_x25519_indexed_last_ladder_elements())
+
+
 def curve25519_dh_CalculatePublicKey(sk, fast=False):
     """n x curve25519_dh_CalculatePublicKey (or _fast).  Returns (pk, clamped_sk)."""
     sk = np.array(_np(sk, 32, "sk"), copy=True)
@@ -264,6 +295,25 @@ def curve25519_dh_CreateSharedKey_one_peer_dev(shared, pk, sk):
             _check(sk, 32, "sk"))
     with _on(sk) as st:
         _lib.check(_lib.load().curve25519_dh_CreateSharedKey_one_peer_dev(*args, n, st), "curve25519_dh_CreateSharedKey_one_peer_dev")
+
+
+def curve25519_dh_Peer_Init_dev(ctx, pk):
+    """Device form of curve25519_dh_Peer_Init: pk uint8[n, 32], ctx uint8[n, 1600]; asynchronous on torch's current stream."""
+    n, d = pk.shape[0], pk.device
+    args = (_check(ctx, PEER_CTX_SIZE, "ctx", n, device=d), _check(pk, 32, "pk"))
+    with _on(pk) as st:
+        _lib.check(_lib.load().curve25519_dh_Peer_Init_dev(*args, n, st), "curve25519_dh_Peer_Init_dev")
+
+
+def curve25519_dh_CreateSharedKey_indexed_dev(shared, ctxs, idx, sk):
+    """Device form of curve25519_dh_CreateSharedKey_indexed: ctxs uint8[n_ctx, 1600], idx int32[n, 1] (read as uint32), writes
+    `shared`, clamps `sk`.  An index >= n_ctx gives 32 zero bytes (nothing is checked on the host); does not synchronise."""
+    import torch
+    n, d = sk.shape[0], sk.device
+    args = (_check(shared, 32, "shared", n, device=d), _check(ctxs, PEER_CTX_SIZE, "ctxs", device=d), ctxs.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sk, 32, "sk"))
+    with _on(sk) as st:
+        _lib.check(_lib.load().curve25519_dh_CreateSharedKey_indexed_dev(*args, n, st), "curve25519_dh_CreateSharedKey_indexed_dev")
 
 
 def curve25519_dh_CalculatePublicKey_dev(pk, sk, fast=False):

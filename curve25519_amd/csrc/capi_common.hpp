@@ -95,6 +95,7 @@ enum Tunable {
     T_QUAD_MIN,                 // calls of MORE than QUAD_MIN and at most QUAD_MAX elements run FOUR LANES per element (quad25519.cuh):
     T_QUAD_MAX,                 //   QUAD_MAX = 0: never; unset: per operation (engine.hip)
     T_ONE_PEER_WIDE,            // curve25519_dh_CreateSharedKey_one_peer: smallest batch that builds a wide comb for a NEW peer key (0: never)
+    T_PEER_INDEXED_MIN,         // curve25519_dh_CreateSharedKey_indexed: smallest batch that walks the contexts' rows (0: always)
     T_COUNT
 };
 constexpr long T_UNSET = -1;
@@ -102,7 +103,7 @@ inline const char* const* tunable_names()
 {
     static const char* const names[T_COUNT] = { "COOP_MAX", "XF_SPLIT", "INV_K", "VERIFY_REFERENCE_ORDER", "MULTI_FORCE_GATHER",
                                                 "MULTI_VIRTUAL", "BASE_COMB", "HELPER_THREADS", "VERIFY_LAT_CAP_BITS", "ONE_KEY_WIDE", "LADDER2_MAX",
-                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE" };
+                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN" };
     return names;
 }
 inline std::atomic<long>* tunable_table()
@@ -237,6 +238,8 @@ struct ThreadState {
     bool vctx_valid = false;
     void* vctxs = nullptr;                 // the n_ctx x 2080 bytes of this thread's last ed25519_Verify_Check_indexed_*batch (grow-only)
     size_t vctxs_cap = 0;
+    void* pctxs = nullptr;                 // the n_ctx x 1600 bytes of this thread's last curve25519_dh_CreateSharedKey_indexed_batch (grow-only)
+    size_t pctxs_cap = 0;
     void* bctx = nullptr;                  // the same for the 192-byte blinding context of this thread's last blinded *_batch call
     unsigned char bctx_host[192] = {};
     bool bctx_valid = false;
@@ -464,6 +467,8 @@ struct ThreadState {
         vctx_valid = false;
         if (vctxs) { (void)hipMemset(vctxs, 0, vctxs_cap); (void)hipFree(vctxs); vctxs = nullptr; }
         vctxs_cap = 0;
+        if (pctxs) { (void)hipMemset(pctxs, 0, pctxs_cap); (void)hipFree(pctxs); pctxs = nullptr; }
+        pctxs_cap = 0;
         if (bctx) { (void)hipMemset(bctx, 0, 192); (void)hipFree(bctx); bctx = nullptr; }
         memset(bctx_host, 0, sizeof bctx_host);
         bctx_valid = false;

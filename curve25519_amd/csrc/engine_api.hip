@@ -326,6 +326,46 @@ int curve25519_dh_CreateSharedKey_one_peer_batch(unsigned char* shared, const un
                      });
 }
 
+int curve25519_dh_Peer_Init_batch(void* ctx, const unsigned char* pk, size_t n)
+{
+    if (!ctx || !pk) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, ctx, 1600 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return curve25519_dh_Peer_Init_dev(d[1], d[0], c, st);
+                     });
+}
+
+// many peer contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
+// uploaded once per call into a grow-only device buffer of the calling thread, the indices travel in pieces with the secrets
+int curve25519_dh_CreateSharedKey_indexed_batch(unsigned char* shared, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                                unsigned char* sk, size_t n)
+{
+    C25519_API_CALL();
+    if (!shared || !ctxs || !ctx_index || !sk) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    if (n_ctx == 0) return bad_arg("no contexts");
+    if (n_ctx > ((size_t)1 << 32)) return bad_arg("more contexts than a uint32 index reaches");
+    for (size_t i = 0; i < n; i++)
+        if (ctx_index[i] >= n_ctx) return bad_arg("context index out of range");
+    ThreadState& t = tls();
+    C25519_RC(t.ensure());
+    const size_t bytes = n_ctx * 1600;
+    if (bytes > t.pctxs_cap) {
+        if (t.pctxs) { C25519_TRY(hipMemset(t.pctxs, 0, t.pctxs_cap)); C25519_TRY(hipFree(t.pctxs)); }
+        t.pctxs = nullptr;
+        t.pctxs_cap = 0;
+        C25519_TRY(hipMalloc(&t.pctxs, bytes));
+        t.pctxs_cap = bytes;
+    }
+    C25519_RC(c25519_host::upload_now(t.pctxs, ctxs, bytes));
+    void* dctxs = t.pctxs;
+    return run_batch(n, { Arr{ sk, sk, 32 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ nullptr, shared, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return curve25519_dh_CreateSharedKey_indexed_dev(d[2], dctxs, n_ctx, d[1], d[0], c, st);
+                     });
+}
+
 static int public_batch(unsigned char* pk, unsigned char* sk, size_t n, bool fast)
 {
     if (!pk || !sk) return bad_arg("null pointer");

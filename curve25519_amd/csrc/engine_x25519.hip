@@ -4,6 +4,7 @@
 // (one of the engine's four translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 #include "x25519_peer.cuh"
+#include "x25519_peer_ctx.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // X25519   (curve25519_dh_CreateSharedKey / curve25519_dh_CalculatePublicKey)
@@ -392,6 +393,81 @@ struct FinishX25519IfWide {
     C25519_DEV void emit(size_t e, const fe& zinv) const { fin.emit(e, zinv); }
 };
 
+// ---- many secrets, MANY peer keys: element i against context ctx_index[i] (x25519_peer_ctx.cuh) -----------------------------
+// curve25519_dh_Peer_Init: one lane per key, its projective rows in lane-private scratch (QTableLimbs) until they are normalised
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VI_WAVES) k_x25519_peer_init(u32* ctxs, const void* pk, size_t n, u32* tables)
+{
+    const size_t i = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    u32 u[8];
+    load32(u, pk, i);
+    peer_ctx_build(ctxs + i * PEER_CTX_WORDS, u, tables + i * QTABLE_LIMB_WORDS);
+}
+
+// the walk over the element's own context rows, read in place; numerator and denominator to the X25519 scratch slots.  An
+// element whose context is not eligible goes on the ladder list (k_x25519_peer_indexed_ladder); an index >= n_ctx leaves
+// num = den = 0, which the shared inversion turns into 32 zero bytes -- the ladder's answer for the key 0.
+__global__ void __launch_bounds__(WB_BLOCK, 4) k_x25519_peer_indexed_walk(ProjScratch scr, void* sk, const u32* __restrict__ ctxs,
+                                                                          size_t n_ctx, const u32* __restrict__ ctx_index, size_t n,
+                                                                          u32* ladder_list, u32* ladder_count)
+{
+    __shared__ u32 cols[8 * WB_BLOCK];                        // the lane's 64 columns (peer_ctx_columns)
+    const size_t i = (size_t)blockIdx.x * WB_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    u32 k[8];
+    load32(k, sk, i);
+    clamp_words(k);
+    store32(sk, i, k);                                        // the reference clamps in the caller's buffer
+    const u32* ctx = peer_ctx_of(ctxs, n_ctx, ctx_index, i);
+    fe num, den;
+    if (ctx && ctx[PEER_CTX_ELIGIBLE] != 1u) {                // (public: which peer, and whether it lies on the curve)
+        ladder_list[atomicAdd(ladder_count, 1u)] = (u32)i;
+        return;
+    }
+    if (ctx) {
+        peer_ctx_columns(cols + threadIdx.x, WB_BLOCK, k);
+        peer_ctx_walk(num, den, cols + threadIdx.x, WB_BLOCK, ctx + PEER_CTX_ROWS);
+    } else {
+        fe_set_u32(num, 0);
+        fe_set_u32(den, 0);
+    }
+    soa_store_fe(scr.a, n, i, num);
+    soa_store_fe(scr.z, n, i, den);
+}
+
+// ... then the ladder for the listed elements, on the key their context holds, into the same scratch slots (the k_ed25519_verify_slow
+// pattern: the grid covers every element, workgroups beyond the list's end read the counter and leave).  report: the list's length
+// for c25519_amd_x25519_indexed_last_ladder_elements.
+__global__ void __launch_bounds__(XL_BLOCK, C25519_XF_WAVES) k_x25519_peer_indexed_ladder(ProjScratch scr, const void* sk, const u32* __restrict__ ctxs,
+                                                                                         const u32* __restrict__ ctx_index, size_t n,
+                                                                                         const u32* __restrict__ ladder_list,
+                                                                                         const u32* __restrict__ ladder_count, u32* report)
+{
+    const u32 count = *ladder_count;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *report = count;
+    const size_t j = (size_t)blockIdx.x * XL_BLOCK + threadIdx.x;
+    if (j >= count) return;
+    const size_t i = ladder_list[j];
+    u32 u[8], k[8];
+    peer_ctx_key(u, ctxs + (size_t)ctx_index[i] * PEER_CTX_WORDS);    // (listed: the index is in range)
+    load32(k, sk, i);                                         // (clamped by the walk kernel)
+    fe PX, PZ;
+    x25519_ladder_xz<false>(PX, PZ, u, k);
+    soa_store_fe(scr.a, n, i, PX);
+    soa_store_fe(scr.z, n, i, PZ);
+}
+
+// the key of each element's context as n records (32 zero bytes for an index >= n_ctx), for a call that runs what
+// curve25519_dh_CreateSharedKey_dev runs: one 16-byte half per thread
+__global__ void __launch_bounds__(256) k_x25519_peer_gather(uint4* keys, const u32* __restrict__ ctxs, size_t n_ctx,
+                                                            const u32* __restrict__ ctx_index, size_t n)
+{
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= 2 * n) return;
+    const u32* ctx = peer_ctx_of(ctxs, n_ctx, ctx_index, g >> 1);
+    keys[g] = ctx ? reinterpret_cast<const uint4*>(ctx)[g & 1] : make_uint4(0, 0, 0, 0);
+}
+
 namespace {
 
 // lanes per X25519 workgroup for a batch of n: the widest shape that still puts a wave on every SIMD the batch can reach
@@ -435,7 +511,8 @@ int c25519_amd_probe_words(void) { return PROBE_WORDS; }
 
 // ---- device-pointer entry points ----------------------------------------------------------------
 
-static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t stream)
+// work: null, or scratch of at least proj_words(n) words the caller holds already (a lease of its own on this stream)
+static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t stream, u32* work = nullptr)
 {
     if (x25519_quad_for(n)) {                                 // four lanes per element
         const unsigned grid = grid_for(n, quad::ELEMS_PER_WAVE);
@@ -453,15 +530,15 @@ static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t
         return 0;
     }
     if (x25519_split_for(n)) {
-        void* w = nullptr;
+        void* w = work;
         c25519_host::WorkLease lease;
-        C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
+        if (!work) C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
         const ProjScratch scr = carve_proj((u32*)w, n);
         if (pk) k_x25519_ladder<false><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         else    k_x25519_ladder<true><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         C25519_TRY(hipGetLastError());
         C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
-        return lease.release();
+        return work ? 0 : lease.release();
     }
     switch (x25519_block_for(n)) {
     case 64:  x25519_launch<64>(out, pk, sk, n, stream); break;
@@ -603,6 +680,115 @@ long c25519_amd_x25519_one_peer_last_wide(void)
     u32 v = 0;
     if (hipMemcpy(&v, lp.wide_ok, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return v ? 1 : 0;
+}
+
+// ---- many secrets, many peer contexts -------------------------------------------------------------------------
+
+// keys per k_x25519_peer_init launch: bounds its lane-private scratch (2.5 KiB per key) at 80 MiB
+constexpr size_t PEER_INIT_CHUNK = (size_t)1 << 15;
+
+int curve25519_dh_Peer_Init_dev(void* ctx, const void* pk, size_t n, void* stream_)
+{
+    C25519_API_CALL();
+    if (!ctx || !pk) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { ctx, pk })) return rc;
+    if (n == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t chunk = std::min(n, PEER_INIT_CHUNK);
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, chunk * QTABLE_LIMB_WORDS * sizeof(u32), stream));
+    for (size_t lo = 0; lo < n; lo += chunk) {
+        const size_t c = std::min(chunk, n - lo);
+        k_x25519_peer_init<<<grid_for(c, ED_BLOCK), ED_BLOCK, 0, stream>>>((u32*)ctx + lo * PEER_CTX_WORDS, (const uint4*)pk + 2 * lo, c,
+                                                                             (u32*)w);
+        C25519_TRY(hipGetLastError());
+    }
+    return lease.release();
+}
+
+// the smallest call that walks the contexts' rows (tunable PEER_INDEXED_MIN; 0 = always).  Up to 2^16 secrets a call of the walk takes
+// one lane's latency, 0.27 ms whatever its size; the per-wave ladder finishes sooner up to 2048 secrets (0.14-0.24 ms) and later from
+// 2304 on (0.28 ms), so a smaller call gathers the keys and runs what curve25519_dh_CreateSharedKey_dev runs at its size
+// (tools/peer_indexed_rate.py, profiles/peer_indexed_rate.txt).
+constexpr long PEER_INDEXED_MIN_DEFAULT = 2049;
+
+// what the calling thread's last indexed call on this device left behind for c25519_amd_x25519_indexed_last_ladder_elements: the
+// elements the host knows ran the ladder (the whole call below PEER_INDEXED_MIN), or the device word the ladder kernel reports in
+struct LastIndexed { long host = -1; const u32* report = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; };
+static thread_local LastIndexed tl_last_indexed;
+
+static int x25519_indexed_dev(void* out, const void* ctxs, size_t n_ctx, const void* ctx_index, void* sk, size_t n, hipStream_t stream)
+{
+    const long min_walk = c25519_host::tunable_or(c25519_host::T_PEER_INDEXED_MIN, PEER_INDEXED_MIN_DEFAULT);
+    const size_t whole = std::max(n, c25519_host::batch_shape_hint());
+    tl_last_indexed = LastIndexed();
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    if (whole < (size_t)std::max(min_walk, 0L)) {
+        const size_t key_words = round_up(8 * n, 4);
+        const bool split = !x25519_quad_for(n) && !x25519_coop_for(n) && x25519_split_for(n);
+        C25519_RC(lease.acquire(&w, (key_words + (split ? proj_words(n) : 0)) * sizeof(u32), stream));
+        k_x25519_peer_gather<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)w, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
+        C25519_TRY(hipGetLastError());
+        bool& zero_copy = c25519_host::zero_copy_call();      // the gathered keys are device memory, not the call's host records
+        const bool zc = zero_copy;
+        zero_copy = false;
+        const int rc = x25519_dev(out, w, sk, n, stream, split ? (u32*)w + key_words : nullptr);
+        zero_copy = zc;
+        C25519_RC(rc);
+        tl_last_indexed.host = (long)n;
+        tl_last_indexed.generation = tls().generation;
+        return lease.release();
+    }
+    unsigned* report = nullptr;
+    C25519_RC(tls().report_word_for(&report, stream));
+    C25519_RC(lease.acquire(&w, (proj_words(n) + round_up(n, 4) + 4) * sizeof(u32), stream));
+    const ProjScratch scr = carve_proj((u32*)w, n);
+    u32* list = (u32*)w + proj_words(n);
+    u32* count = list + round_up(n, 4);
+    C25519_TRY(hipMemsetAsync(count, 0, sizeof(u32), stream));
+    k_x25519_peer_indexed_walk<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(scr, sk, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n,
+                                                                              list, count);
+    C25519_TRY(hipGetLastError());
+    k_x25519_peer_indexed_ladder<<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr, sk, (const u32*)ctxs, (const u32*)ctx_index, n,
+                                                                                list, count, report + 1);
+    C25519_TRY(hipGetLastError());
+    C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
+    tl_last_indexed.report = report + 1;                      // (word 0 is the fast verification's slow-list report)
+    tl_last_indexed.stream = stream;
+    tl_last_indexed.generation = tls().generation;
+    (void)hipGetDevice(&tl_last_indexed.device);
+    return lease.release();
+}
+
+int curve25519_dh_CreateSharedKey_indexed_dev(void* shared, const void* ctxs, size_t n_ctx, const void* ctx_index, void* sk, size_t n,
+                                              void* stream)
+{
+    C25519_API_CALL();
+    if (!shared || !ctxs || !ctx_index || !sk) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { shared, ctxs, ctx_index, sk })) return rc;
+    if (n == 0) return 0;
+    if (n_ctx == 0) return bad_arg("no contexts");
+    return x25519_indexed_dev(shared, ctxs, n_ctx, ctx_index, sk, n, (hipStream_t)stream);
+}
+
+// test / accounting hook: how many elements of the calling thread's last indexed call on this device ran the ladder -- all of them
+// below PEER_INDEXED_MIN, otherwise those whose context is not eligible.  -1: no such call.  Synchronises with that call's stream.
+// (A *_batch call of several pieces reports its last piece.)
+long c25519_amd_x25519_indexed_last_ladder_elements(void)
+{
+    C25519_API_CALL_OR(-1);
+    const LastIndexed& li = tl_last_indexed;
+    if (li.generation != tls().generation) return -1;        // (c25519_amd_thread_release() / a device switch since)
+    if (li.host >= 0) return li.host;
+    if (!li.report) return -1;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != li.device) return -1;
+    if (hipStreamSynchronize(li.stream) != hipSuccess) return -1;
+    u32 v = 0;
+    if (hipMemcpy(&v, li.report, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (long)v;
 }
 
 }  // extern "C"

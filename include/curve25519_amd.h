@@ -51,7 +51,9 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * one-key ed25519_Verify_Check_* with a comb: the whole operation in one launch, defaults 1024 / 16384; QUAD_MAX = 0: never),
  * ONE_PEER_WIDE (curve25519_dh_CreateSharedKey_one_peer_*: the smallest batch that BUILDS a wide comb for a new peer key; a call
  * of more than 3584 elements with the peer the calling thread's last comb was built for walks that comb whatever its size;
- * default 98304; 0 = never).
+ * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
+ * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
+ * 0 = always walk).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -103,6 +105,44 @@ int curve25519_dh_CreateSharedKey_one_peer_dev(void *shared, const void *pk /* 3
 /* did the calling thread's last curve25519_dh_CreateSharedKey_one_peer_* call on this device walk the peer's comb (1) or the
  * ladder (0)?  -1: no such call.  Synchronises with that call's stream.  (A *_batch call of several pieces reports its last piece.) */
 long c25519_amd_x25519_one_peer_last_wide(void);
+
+/* X25519 against MANY peer keys in one call: a mixed stream of secrets, each against one of n_ctx known peers (static-static DH
+ * with configured peers, records sealed to many recipients).  A peer context is C25519_AMD_PEER_CTX_SIZE bytes, deterministic
+ * (the same key always gives the same bytes) and free of pointers (it may be copied or stored):
+ *   bytes 0..31     the peer key exactly as given (the ladder reads it)
+ *   bytes 32..35    uint32 eligibility: 1 = the rows stand in for the ladder, 0 = the ladder decides
+ *   bytes 36..63    zero
+ *   bytes 64..1599  16 rows of 96 bytes.  Row k = sum over the set bits i of k of 2^(64 i) * Q, Q = 8 * P, P the point of u = the
+ *                   key read as 256 bits mod p (x the root ed25519's decoding picks for parity 0), affine (Z = 1), stored as
+ *                   Y+X | Y-X | 2d*X*Y, three field elements of eight canonical little-endian 32-bit words.  Row 0 is (1, 1, 0).
+ *                   A small-order P has 16 neutral rows (its shared keys are 0, as from the ladder).  A key on the twist, and
+ *                   u = -1, have eligibility 0 and zero rows.
+ * A context is trusted data, like a key store: a modified context gives an unspecified output, and since its rows need not lie
+ * in the curve's prime-order subgroup, it can reveal bits of the secret to whoever chose them.  It still reads nothing outside
+ * ctxs.  The index is public data: its gather is not constant-time; the secret only selects rows.
+ * curve25519_dh_CreateSharedKey_indexed_*: n x curve25519_dh_CreateSharedKey(shared_i, ctxs[ctx_index[i]].pk, sk_i), sk clamped
+ * in place; every output byte and clamped sk byte equals what curve25519_dh_CreateSharedKey_* gives for the key in the element's
+ * context.  ctx_index is n x uint32.
+ *   n == 0 returns 0; a null pointer, or n_ctx == 0 with n > 0, is an argument error.
+ *   *_batch checks every index on the host: one >= n_ctx refuses the call before any work, shared and sk untouched.  It uploads
+ *   the contexts once per call into a device buffer of the calling thread (grow-only; zeroed before it is freed by
+ *   c25519_amd_thread_release() or a larger call).
+ *   *_dev never synchronises: an index >= n_ctx is a context for the key 0 (32 zero bytes, sk still clamped) and nothing outside
+ *   ctxs is read.
+ * From PEER_INDEXED_MIN elements per call (tunable, see above) each element walks its own context's rows in place (64 doublings
+ * and 64 mixed additions); elements of ineligible contexts run the ladder in a second kernel.  Smaller calls gather the keys and
+ * run what curve25519_dh_CreateSharedKey_dev runs at their size (profiles/peer_indexed_rate.txt). */
+#define C25519_AMD_PEER_CTX_SIZE 1600
+int curve25519_dh_Peer_Init_batch(void *ctx, const unsigned char *pk, size_t n);          /* n x 1600 bytes */
+int curve25519_dh_Peer_Init_dev(void *ctx, const void *pk, size_t n, void *stream);
+int curve25519_dh_CreateSharedKey_indexed_batch(unsigned char *shared, const void *ctxs, size_t n_ctx,
+                                                const uint32_t *ctx_index, unsigned char *sk, size_t n);
+int curve25519_dh_CreateSharedKey_indexed_dev(void *shared, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                              void *sk, size_t n, void *stream);
+/* how many elements of the calling thread's last curve25519_dh_CreateSharedKey_indexed_* call on this device ran the ladder (all of
+ * them below PEER_INDEXED_MIN, else those of ineligible contexts)?  -1: no such call.  Synchronises with that call's stream.  (A
+ * *_batch call of several pieces reports its last piece.) */
+long c25519_amd_x25519_indexed_last_ladder_elements(void);
 
 /* n x curve25519_dh_CalculatePublicKey (reference :34): ladder on the base point u = 9 */
 int curve25519_dh_CalculatePublicKey_batch(unsigned char *pk, unsigned char *sk, size_t n);
