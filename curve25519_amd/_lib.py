@@ -30,6 +30,12 @@ SIGNATURES = {
     "ed25519_SignMessage_dev": [_vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_SignMessage_ragged_batch": [_vp, _vp, _vp, _vp, _sz],
     "ed25519_SignMessage_ragged_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_Sign_Init_batch": [_vp, _vp, _sz],
+    "ed25519_Sign_Init_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_SignMessage_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _sz, _sz],
+    "ed25519_SignMessage_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_SignMessage_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz],
+    "ed25519_SignMessage_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

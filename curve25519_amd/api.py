@@ -147,6 +147,40 @@ def ed25519_SignMessage_ragged(priv, messages):
     return sig
 
 
+SIGN_CTX_SIZE = 128
+
+
+def ed25519_Sign_Init(priv):
+    """n x ed25519_Sign_Init: signer contexts, uint8[n, 128] (a || prefix || pk || 0).  As secret as the private keys."""
+    priv = _np(priv, 64, "priv")
+    ctx = np.empty((priv.shape[0], SIGN_CTX_SIZE), np.uint8)
+    _lib.check(_lib.load().ed25519_Sign_Init_batch(_ptr(ctx), _ptr(priv), priv.shape[0]), "ed25519_Sign_Init_batch")
+    return ctx
+
+
+def ed25519_SignMessage_indexed(ctxs, idx, msg):
+    """Many keys in one call: uint8[n_ctx, 128] contexts (Sign_Init's), uint32[n] indices, fixed-length messages msg[n, msg_size] ->
+    uint8[n, 64], signature i as ed25519_SignMessage under the key of context idx[i].  An index >= n_ctx raises EngineError."""
+    n = np.size(idx)
+    ctxs, idx = _ctx_index(ctxs, idx, n, SIGN_CTX_SIZE, "message")
+    msg, msg_size = _msgs(msg, n)
+    sig = np.empty((n, 64), np.uint8)
+    _lib.check(_lib.load().ed25519_SignMessage_indexed_batch(_ptr(sig), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(msg), msg_size, n),
+               "ed25519_SignMessage_indexed_batch")
+    return sig
+
+
+def ed25519_SignMessage_indexed_ragged(ctxs, idx, messages):
+    """ed25519_SignMessage_indexed with per-element message lengths (`messages`: sequence of bytes-like)."""
+    n = len(messages)
+    ctxs, idx = _ctx_index(ctxs, idx, n, SIGN_CTX_SIZE, "message")
+    flat, offsets = _ragged(messages)
+    sig = np.empty((n, 64), np.uint8)
+    _lib.check(_lib.load().ed25519_SignMessage_indexed_ragged_batch(_ptr(sig), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(flat),
+                                                                     _ptr(offsets), n), "ed25519_SignMessage_indexed_ragged_batch")
+    return sig
+
+
 def ed25519_VerifySignature_ragged(sig, pk, messages):
     sig = _np(sig, 64, "sig")
     pk = _np(pk, 32, "pk")
@@ -196,11 +230,11 @@ def ed25519_Verify_Check(ctx, sig, msg):
     return ok
 
 
-def _ctx_index(ctxs, idx, n):
-    ctxs = _np(ctxs, 2080, "ctxs") if np.size(ctxs) else np.zeros((0, 2080), np.uint8)
+def _ctx_index(ctxs, idx, n, width=2080, what="signature"):
+    ctxs = _np(ctxs, width, "ctxs") if np.size(ctxs) else np.zeros((0, width), np.uint8)
     idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
     if idx.size != n:
-        raise ValueError("one context index per signature")
+        raise ValueError(f"one context index per {what}")
     return ctxs, idx
 
 
@@ -337,6 +371,25 @@ def ed25519_SignMessage_dev(sig, priv, msg):
     args = (_check(sig, 64, "sig", n, device=d), _check(priv, 64, "priv"), _check(msg, None, "msg", n, device=d))
     with _on(priv) as st:
         _lib.check(_lib.load().ed25519_SignMessage_dev(*args, msg.shape[1], n, st), "ed25519_SignMessage_dev")
+
+
+def ed25519_Sign_Init_dev(ctx, priv):
+    """Device form of ed25519_Sign_Init: priv uint8[n, 64], ctx uint8[n, 128]; asynchronous on torch's current stream."""
+    n, d = priv.shape[0], priv.device
+    args = (_check(ctx, SIGN_CTX_SIZE, "ctx", n, device=d), _check(priv, 64, "priv"))
+    with _on(priv) as st:
+        _lib.check(_lib.load().ed25519_Sign_Init_dev(*args, n, st), "ed25519_Sign_Init_dev")
+
+
+def ed25519_SignMessage_indexed_dev(sig, ctxs, idx, msg):
+    """Device form of ed25519_SignMessage_indexed: ctxs uint8[n_ctx, 128], idx int32[n, 1] (read as uint32), msg uint8[n, msg_size],
+    sig uint8[n, 64].  An index >= n_ctx gives 64 zero bytes (nothing is checked on the host); does not synchronise."""
+    import torch
+    n, d = msg.shape[0], msg.device
+    args = (_check(sig, 64, "sig", n, device=d), _check(ctxs, SIGN_CTX_SIZE, "ctxs", device=d), ctxs.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(msg, None, "msg", n, device=d))
+    with _on(msg) as st:
+        _lib.check(_lib.load().ed25519_SignMessage_indexed_dev(*args, msg.shape[1], n, st), "ed25519_SignMessage_indexed_dev")
 
 
 def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):

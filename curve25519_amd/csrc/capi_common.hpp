@@ -240,6 +240,8 @@ struct ThreadState {
     size_t vctxs_cap = 0;
     void* pctxs = nullptr;                 // the n_ctx x 1600 bytes of this thread's last curve25519_dh_CreateSharedKey_indexed_batch (grow-only)
     size_t pctxs_cap = 0;
+    void* sctxs = nullptr;                 // the n_ctx x 128 bytes of this thread's last ed25519_SignMessage_indexed_*batch (grow-only; secret)
+    size_t sctxs_cap = 0;
     void* bctx = nullptr;                  // the same for the 192-byte blinding context of this thread's last blinded *_batch call
     unsigned char bctx_host[192] = {};
     bool bctx_valid = false;
@@ -469,6 +471,8 @@ struct ThreadState {
         vctxs_cap = 0;
         if (pctxs) { (void)hipMemset(pctxs, 0, pctxs_cap); (void)hipFree(pctxs); pctxs = nullptr; }
         pctxs_cap = 0;
+        if (sctxs) { (void)hipMemset(sctxs, 0, sctxs_cap); (void)hipFree(sctxs); sctxs = nullptr; }
+        sctxs_cap = 0;
         if (bctx) { (void)hipMemset(bctx, 0, 192); (void)hipFree(bctx); bctx = nullptr; }
         memset(bctx_host, 0, sizeof bctx_host);
         bctx_valid = false;

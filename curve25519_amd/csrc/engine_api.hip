@@ -622,23 +622,25 @@ int ed25519_Verify_Check_batch(int* verdict, const void* ctx, const unsigned cha
 }
 
 // many contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
-// uploaded once per call into a grow-only device buffer of the calling thread, the indices travel in pieces with the pairs
-static int indexed_prepare(ThreadState& t, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index, size_t n)
+// uploaded once per call into a grow-only device buffer of the calling thread (`buf`, `cap`: the verification contexts' or the signer
+// contexts'), the indices travel in pieces with the elements
+static int indexed_prepare(ThreadState& t, void*& buf, size_t& cap, size_t ctx_bytes, const void* ctxs, size_t n_ctx,
+                           const uint32_t* ctx_index, size_t n)
 {
     if (n_ctx == 0) return bad_arg("no contexts");
     if (n_ctx > ((size_t)1 << 32)) return bad_arg("more contexts than a uint32 index reaches");
     for (size_t i = 0; i < n; i++)
         if (ctx_index[i] >= n_ctx) return bad_arg("context index out of range");
     C25519_RC(t.ensure());
-    const size_t bytes = n_ctx * 2080;
-    if (bytes > t.vctxs_cap) {
-        if (t.vctxs) { C25519_TRY(hipMemset(t.vctxs, 0, t.vctxs_cap)); C25519_TRY(hipFree(t.vctxs)); }
-        t.vctxs = nullptr;
-        t.vctxs_cap = 0;
-        C25519_TRY(hipMalloc(&t.vctxs, bytes));
-        t.vctxs_cap = bytes;
+    const size_t bytes = n_ctx * ctx_bytes;
+    if (bytes > cap) {
+        if (buf) { C25519_TRY(hipMemset(buf, 0, cap)); C25519_TRY(hipFree(buf)); }
+        buf = nullptr;
+        cap = 0;
+        C25519_TRY(hipMalloc(&buf, bytes));
+        cap = bytes;
     }
-    return c25519_host::upload_now(t.vctxs, ctxs, bytes);
+    return c25519_host::upload_now(buf, ctxs, bytes);
 }
 
 int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
@@ -648,7 +650,7 @@ int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_
     if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
     ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, ctxs, n_ctx, ctx_index, n));
+    C25519_RC(indexed_prepare(t, t.vctxs, t.vctxs_cap, 2080, ctxs, n_ctx, ctx_index, n));
     void* dctxs = t.vctxs;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
@@ -664,7 +666,7 @@ int ed25519_Verify_Check_indexed_ragged_batch(int* verdict, const void* ctxs, si
     if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
     ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, ctxs, n_ctx, ctx_index, n));
+    C25519_RC(indexed_prepare(t, t.vctxs, t.vctxs_cap, 2080, ctxs, n_ctx, ctx_index, n));
     const int L = ThreadState::LANES - 1;
     hipStream_t st = t.stream[L];
     void *d_msgs, *d_off;
@@ -677,6 +679,53 @@ int ed25519_Verify_Check_indexed_ragged_batch(int* verdict, const void* ctxs, si
     C25519_RC(ed25519_Verify_Check_indexed_ragged_dev(t.dbuf[L][2], t.vctxs, n_ctx, t.dbuf[L][1], t.dbuf[L][0], d_msgs,
                                                       (const uint64_t*)d_off, n, st));
     C25519_TRY(hipMemcpyAsync(verdict, t.dbuf[L][2], sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    C25519_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)
+{
+    if (!ctx || !priv) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ nullptr, ctx, 128 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_Sign_Init_dev(d[1], d[0], c, st);
+                     });
+}
+
+// signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
+int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                      const unsigned char* msg, size_t msg_size, size_t n)
+{
+    C25519_API_CALL();
+    if (!sig || !ctxs || !ctx_index || (!msg && msg_size)) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    ThreadState& t = tls();
+    C25519_RC(indexed_prepare(t, t.sctxs, t.sctxs_cap, 128, ctxs, n_ctx, ctx_index, n));
+    void* dctxs = t.sctxs;
+    return run_batch(n, { Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, sig, 64 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_SignMessage_indexed_dev(d[2], dctxs, n_ctx, d[0], d[1], msg_size, c, st);
+                     });
+}
+
+int ed25519_SignMessage_indexed_ragged_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                             const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    C25519_API_CALL();
+    if (!sig || !ctxs || !ctx_index || !offsets) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    ThreadState& t = tls();
+    C25519_RC(indexed_prepare(t, t.sctxs, t.sctxs_cap, 128, ctxs, n_ctx, ctx_index, n));
+    const int L = ThreadState::LANES - 1;
+    hipStream_t st = t.stream[L];
+    void *d_msgs, *d_off;
+    C25519_RC(ragged_upload(t, &d_msgs, &d_off, msgs, offsets, n));
+    C25519_RC(t.reserve_dev(L, 0, sizeof(uint32_t) * n));
+    C25519_RC(t.reserve_dev(L, 1, 64 * n));
+    C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], ctx_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    C25519_RC(ed25519_SignMessage_indexed_ragged_dev(t.dbuf[L][1], t.sctxs, n_ctx, t.dbuf[L][0], d_msgs, (const uint64_t*)d_off, n, st));
+    C25519_TRY(hipMemcpyAsync(sig, t.dbuf[L][1], 64 * n, hipMemcpyDeviceToHost, st));
     C25519_TRY(hipStreamSynchronize(st));
     return 0;
 }

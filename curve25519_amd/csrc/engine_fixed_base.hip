@@ -2,6 +2,7 @@
 // signatures, curve25519_dh_CalculatePublicKey_fast, blinding contexts -- kernels and *_dev entry points
 // (one of the engine's four translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
+#include "sign_ctx.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // 8-fold base table, generated on the device at first use
@@ -296,6 +297,77 @@ k_ed25519_sign_quad(void* sig, const void* priv, Msgs msgs, size_t n, const u32*
     quad::sign_element(sig, priv, msgs.ptr(e), msgs.len(e), e, g_wide, cols + threadIdx.x, 64);
 }
 
+// ---- signatures against many signer contexts in one call (sign_ctx.cuh): the three forms above, the key from the element's context --
+// ed25519_Sign_Init: one lane per key
+__global__ void __launch_bounds__(ED_BLOCK) k_ed25519_sign_ctx_init(void* ctxs, const void* priv, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    sign_ctx_init_lane(ctxs, priv, i);
+}
+
+// one lane per element, first part: r = H(prefix || m) mod L, R = r*B projective (a stays in the context: no scratch copy)
+template <bool WIDE>
+__global__ void __launch_bounds__(BaseComb<WIDE>::BLOCK, 4) k_ed25519_sign_indexed_mult(ProjScratch scr, u32* r_out,
+                                                                                         const u32* __restrict__ ctxs, size_t n_ctx,
+                                                                                         const u32* __restrict__ ctx_index, Msgs msgs,
+                                                                                         size_t n, const u32* __restrict__ g_tbl)
+{
+    C25519_BASE_COMB_SETUP(comb);
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 r[8];
+    sign_ctx_nonce_lane(r, sign_ctx_of(ctxs, n_ctx, ctx_index, i), msgs, i);
+    soa_store8(r_out, n, i, r);
+    ge_ext S;
+    comb.template mult<false>(S, r, g_tbl, nullptr);
+    store_proj(scr, n, i, S);
+}
+
+// ... last part, behind the shared inversion (enc(R) in sig[0..31]): S with the context's a and pk
+__global__ void __launch_bounds__(ED_BLOCK, 2) k_ed25519_sign_indexed_finish(void* sig, const u32* __restrict__ ctxs, size_t n_ctx,
+                                                                              const u32* __restrict__ ctx_index, Msgs msgs, size_t n, u32* r_in)
+{
+    const size_t i = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    sign_ctx_finish_lane(sig, sign_ctx_of(ctxs, n_ctx, ctx_index, i), msgs, n, i, r_in);
+}
+
+// one element per two-wave workgroup (k_ed25519_sign_coop without H(seed): the helper serves one compression less)
+template <bool WIDE>
+__global__ void __launch_bounds__(COOP_SHA_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4)))
+k_ed25519_sign_indexed_coop(void* sig, const u32* __restrict__ ctxs, size_t n_ctx, const u32* __restrict__ ctx_index, Msgs msgs, size_t n,
+                            const u32* __restrict__ g_tbl, DoneWord done)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[coop::LDS_WORDS];
+    __shared__ u64 sha_wk[80];
+    if (blockIdx.x >= n) return;
+    const u32* ctx = sign_ctx_of(ctxs, n_ctx, ctx_index, blockIdx.x);
+    if (!ctx) {
+        if (threadIdx.x == 0) {
+            sign_ctx_zero_sig(sig, blockIdx.x);
+            signal_done(done);
+        }
+        return;
+    }
+    if (threadIdx.x >= 64) {                               // H(prefix || m), H(enc(R) || pk || m)
+        coop::sha_schedule_server(sha_wk, coop::sign_ctx_sha_blocks(msgs.len(blockIdx.x)));
+        return;
+    }
+    coop::sign_ctx_one<WIDE>(lds, coop::make_lane(threadIdx.x), sig, ctx, msgs, blockIdx.x, g_tbl, &done, coop::ShaTwoWaves{ sha_wk });
+}
+
+// four lanes per element
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
+k_ed25519_sign_indexed_quad(void* sig, const u32* __restrict__ ctxs, size_t n_ctx, const u32* __restrict__ ctx_index, Msgs msgs, size_t n,
+                            const u32* __restrict__ g_wide)
+{
+    __shared__ unsigned short cols[WB_COLS * 64];
+    const size_t e = (size_t)blockIdx.x * quad::ELEMS_PER_WAVE + (threadIdx.x >> 2);
+    if (e >= n) return;
+    quad::sign_ctx_element(sig, sign_ctx_of(ctxs, n_ctx, ctx_index, e), msgs.ptr(e), msgs.len(e), e, g_wide, cols + threadIdx.x, 64);
+}
+
 // ed25519_Blinding_Init (ed25519_sign.c:289-331) for one context: digest = SHA-512(domain || seed),
 // t = digest[0..31] mod L, bl = L - t, zr = digest[32..63], BP = PE(t*B).  One lane does the arithmetic; the
 // workgroup only stages the base tables.  The domain string replaces the reference's compiled-in custom blinder
@@ -561,6 +633,90 @@ int ed25519_SignMessage_ragged_dev(void* sig, const void* priv, const void* msgs
     if (!sig || !priv || !offsets) return bad_arg("null pointer");
     return sign_dev(sig, priv, nullptr, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
                     (hipStream_t)stream);
+}
+
+int ed25519_Sign_Init_dev(void* ctx, const void* priv, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!ctx || !priv) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { ctx, priv })) return rc;
+    if (n == 0) return 0;
+    k_ed25519_sign_ctx_init<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, (hipStream_t)stream>>>(ctx, priv, n);
+    C25519_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// n x ed25519_SignMessage under ctxs + 128 * ctx_index[i]: sign_dev's dispatch (the same tunables, read once per call), the key from
+// the element's context.  An index >= n_ctx gives 64 zero bytes (the device cannot refuse the call without a synchronise).  The
+// contexts are never carried in kernel arguments (no CallWords).
+static int sign_indexed_dev(void* sig, const void* ctxs_, size_t n_ctx, const void* ctx_index_, Msgs msgs, size_t n, hipStream_t stream)
+{
+    if (int rc = check_dev_args(n, { sig, ctxs_, ctx_index_ })) return rc;
+    if (n == 0) return 0;
+    if (n_ctx == 0) return bad_arg("no contexts");
+    const u32* ctxs = (const u32*)ctxs_;
+    const u32* ctx_index = (const u32*)ctx_index_;
+    const u32* tbl = nullptr;
+    C25519_RC(base_tables(&tbl, nullptr));
+    const bool wide_comb = base_comb_wide();
+    if (wide_comb && fixed_base_quad_for(n)) {
+        const u32* wide = nullptr;
+        C25519_RC(wide_tables(&wide));
+        k_ed25519_sign_indexed_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(sig, ctxs, n_ctx, ctx_index, msgs, n, wide);
+        C25519_TRY(hipGetLastError());
+        return 0;
+    }
+    if (fixed_base_coop_for(n)) {
+        if (wide_comb) {
+            const u32* wide = nullptr;
+            C25519_RC(wide_tables(&wide));
+            k_ed25519_sign_indexed_coop<true><<<(unsigned)n, COOP_SHA_BLOCK, 0, stream>>>(sig, ctxs, n_ctx, ctx_index, msgs, n, wide,
+                                                                                          take_done_word(n));
+        } else k_ed25519_sign_indexed_coop<false><<<(unsigned)n, COOP_SHA_BLOCK, 0, stream>>>(sig, ctxs, n_ctx, ctx_index, msgs, n, tbl,
+                                                                                              take_done_word(n));
+        C25519_TRY(hipGetLastError());
+        return 0;
+    }
+    void* w = nullptr;
+    const size_t sc_words = round_up(8 * n, 4);
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, (proj_words(n) + sc_words) * sizeof(u32), stream));
+    const ProjScratch scr = carve_proj((u32*)w, n);
+    u32* r_buf = (u32*)w + proj_words(n);
+    if (wide_comb) {
+        const u32* wide = nullptr;
+        C25519_RC(wide_tables(&wide));
+        k_ed25519_sign_indexed_mult<true><<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(scr, r_buf, ctxs, n_ctx, ctx_index, msgs, n, wide);
+    } else {
+        k_ed25519_sign_indexed_mult<false><<<grid_for(n, bm_block_for(n)), bm_block_for(n), 0, stream>>>(scr, r_buf, ctxs, n_ctx, ctx_index,
+                                                                                                         msgs, n, tbl);
+    }
+    C25519_TRY(hipGetLastError());
+    C25519_RC(launch_invert(scr, n, FinishPack{ scr.a, scr.b, sig, n, 2, 0, nullptr, 0, 0 }, stream));   // sig[e][0..31] = enc(R)
+    k_ed25519_sign_indexed_finish<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(sig, ctxs, n_ctx, ctx_index, msgs, n, r_buf);
+    C25519_TRY(hipGetLastError());
+    return lease.release();
+}
+
+extern "C" {
+
+int ed25519_SignMessage_indexed_dev(void* sig, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* msg, size_t msg_size,
+                                    size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!sig || !ctxs || !ctx_index || (!msg && msg_size)) return bad_arg("null pointer");
+    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream);
+}
+
+int ed25519_SignMessage_indexed_ragged_dev(void* sig, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* msgs,
+                                           const uint64_t* offsets, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!sig || !ctxs || !ctx_index || !offsets) return bad_arg("null pointer");
+    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
+                            (hipStream_t)stream);
 }
 
 // one 192-byte blinding context from seed[0..seed_len) (device pointers)

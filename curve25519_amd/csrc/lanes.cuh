@@ -87,17 +87,25 @@ C25519_DEV void ed_expand_seed(u32 (&a)[8], u64 (&b_words)[4], const u32 (&seed)
     for (int i = 0; i < 4; i++) b_words[i] = dg[4 + i];
 }
 
-// first part of ed25519_SignMessage (:385-397): a = clamp(H(sk)[0..31]), r = H(H(sk)[32..63] || m) mod L, canonical
+// r = H(prefix || m) mod L, canonical; the prefix H(sk)[32..63] as 4 big-endian stream words   (:392-397)
 template <typename Sha = ShaPlain>
-C25519_DEV void ed_sign_nonce(u32 (&a)[8], u32 (&r)[8], const u32 (&seed)[8], const uint8_t* msg, size_t len, const Sha& sha = Sha())
+C25519_DEV void ed_sign_r(u32 (&r)[8], const u64 (&b_words)[4], const uint8_t* msg, size_t len, const Sha& sha = Sha())
 {
-    u64 b_words[4], dg[8];
+    u64 dg[8];
     u32 le[16];
-    ed_expand_seed(a, b_words, seed, sha);
     sha512_prefixed<4>(dg, b_words, msg, len, sha);
     sha512_digest_le_words(le, dg);
     sc_reduce512(r, le);
     sc_mod(r);
+}
+
+// first part of ed25519_SignMessage (:385-397): a = clamp(H(sk)[0..31]), r = H(H(sk)[32..63] || m) mod L, canonical
+template <typename Sha = ShaPlain>
+C25519_DEV void ed_sign_nonce(u32 (&a)[8], u32 (&r)[8], const u32 (&seed)[8], const uint8_t* msg, size_t len, const Sha& sha = Sha())
+{
+    u64 b_words[4];
+    ed_expand_seed(a, b_words, seed, sha);
+    ed_sign_r(r, b_words, msg, len, sha);
 }
 
 // h = H(enc(R) || pk || m) reduced to 256 bits, congruent mod L (not canonical)   (:404-409 / ed25519_verify.c:298-305)

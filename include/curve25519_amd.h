@@ -186,6 +186,38 @@ int ed25519_SignMessage_ragged_batch(unsigned char *sig, const unsigned char *pr
 int ed25519_SignMessage_ragged_dev(void *sig, const void *priv, const void *msgs, const uint64_t *offsets,
                                    size_t n, void *stream);
 
+/* Signing under MANY keys in one call: a mixed stream of messages, each naming one of n_ctx signer contexts (a signing service
+ * with a key store).  A signer context is C25519_AMD_SIGN_CTX_SIZE bytes, built by ed25519_Sign_Init_* from the 64-byte privKey
+ * (seed || pk); deterministic and free of pointers:
+ *   bytes 0..31     a = SHA-512(seed)[0..31] after ecp_TrimSecretKey (the clamped scalar), little-endian
+ *   bytes 32..63    prefix = SHA-512(seed)[32..63]
+ *   bytes 64..95    pk = privKey[32..63] as given (not recomputed: the reference hashes the given half)
+ *   bytes 96..127   zero
+ * A context is as secret as the private key it came from.  A context with other bytes is still defined: element i's signature
+ * is R = r*B, S = (h*a + r) mod L with r = H(prefix || m) mod L and h = H(enc(R) || pk || m), using the context's a (any
+ * 256-bit value), prefix and pk; bytes 96..127 are ignored.  The index is public data: its gather is not constant-time; the
+ * secret only enters the hashes and the comb walk, as in ed25519_SignMessage_*.
+ * ed25519_SignMessage_indexed_*: signature i is byte-identical to ed25519_SignMessage_*(priv[ctx_index[i]], m_i) when the contexts
+ * came from ed25519_Sign_Init_* on priv -- for every priv, one whose pk half is not its seed's included.  ctx_index is n x uint32.
+ *   n == 0 returns 0; a null pointer, or n_ctx == 0 with n > 0, is an argument error.
+ *   *_batch checks every index on the host: one >= n_ctx refuses the call before any work, sig untouched.  It uploads the
+ *   contexts once per call into a device buffer of the calling thread (grow-only; zeroed before it is freed by
+ *   c25519_amd_thread_release() or a larger call).
+ *   *_dev never synchronises: an index >= n_ctx gives 64 zero bytes and nothing outside ctxs is read.
+ * The calls run the forms ed25519_SignMessage_dev runs at their size (the same tunables) without the per-signature SHA-512 of
+ * the seed; a context is never carried in kernel arguments (profiles/sign_indexed_rate.txt). */
+#define C25519_AMD_SIGN_CTX_SIZE 128
+int ed25519_Sign_Init_batch(void *ctx, const unsigned char *priv, size_t n);          /* n x 64 -> n x 128 bytes */
+int ed25519_Sign_Init_dev(void *ctx, const void *priv, size_t n, void *stream);
+int ed25519_SignMessage_indexed_batch(unsigned char *sig, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                      const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_SignMessage_indexed_dev(void *sig, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                    const void *msg, size_t msg_size, size_t n, void *stream);
+int ed25519_SignMessage_indexed_ragged_batch(unsigned char *sig, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                             const unsigned char *msgs, const uint64_t *offsets, size_t n);
+int ed25519_SignMessage_indexed_ragged_dev(void *sig, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                           const void *msgs, const uint64_t *offsets, size_t n, void *stream);
+
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
  * element through the reference's own operation order in a kernel behind the walk.  Measured at n = 2^20
