@@ -40,6 +40,10 @@ SIGNATURES = {
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
     "ed25519_VerifySignature_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VerifySignature_strict_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VerifySignature_strict_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VerifySignature_strict_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_VerifySignature_strict_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],
@@ -49,6 +53,8 @@ SIGNATURES = {
     "ed25519_Verify_Init_dev": [_vp, _vp, _sz, _vp],
     "ed25519_Verify_Check_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
     "ed25519_Verify_Check_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_Verify_Check_strict_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_strict_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_Verify_Check_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
     "ed25519_Verify_Check_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_Verify_Check_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],

@@ -181,7 +181,7 @@ def ed25519_SignMessage_indexed_ragged(ctxs, idx, messages):
     return sig
 
 
-def ed25519_VerifySignature_ragged(sig, pk, messages):
+def ed25519_VerifySignature_ragged(sig, pk, messages, strict=False):
     sig = _np(sig, 64, "sig")
     pk = _np(pk, 32, "pk")
     n = sig.shape[0]
@@ -189,12 +189,23 @@ def ed25519_VerifySignature_ragged(sig, pk, messages):
         raise ValueError("one message and one key per signature")
     flat, offsets = _ragged(messages)
     ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_VerifySignature_ragged_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(flat), _ptr(offsets), n),
-               "ed25519_VerifySignature_ragged_batch")
+    name = "ed25519_VerifySignature_strict_ragged_batch" if strict else "ed25519_VerifySignature_ragged_batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(flat), _ptr(offsets), n), name)
     return ok
 
 
-def ed25519_VerifySignature(sig, pk, msg):
+def ed25519_VerifySignature_strict_ragged(sig, pk, messages):
+    """ed25519_VerifySignature_strict with per-element message lengths (`messages`: sequence of bytes-like)."""
+    return ed25519_VerifySignature_ragged(sig, pk, messages, strict=True)
+
+
+def ed25519_VerifySignature_strict(sig, pk, msg):
+    """n x strict verification (include/curve25519_amd.h: rules 1-6 -- S < L, a canonical key on the curve and not of small order,
+    R not of small order, and the reference's verdict).  Returns int32[n] of 1 (valid) / 0 (invalid or rejected)."""
+    return ed25519_VerifySignature(sig, pk, msg, strict=True)
+
+
+def ed25519_VerifySignature(sig, pk, msg, strict=False):
     """n x ed25519_VerifySignature.  Returns int32[n] of 1 (valid) / 0 (invalid)."""
     sig = _np(sig, 64, "sig")
     pk = _np(pk, 32, "pk")
@@ -203,8 +214,8 @@ def ed25519_VerifySignature(sig, pk, msg):
         raise ValueError("sig and pk must have the same number of rows")
     msg, msg_size = _msgs(msg, n)
     ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_VerifySignature_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n),
-               "ed25519_VerifySignature_batch")
+    name = "ed25519_VerifySignature_strict_batch" if strict else "ed25519_VerifySignature_batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n), name)
     return ok
 
 
@@ -216,7 +227,12 @@ def ed25519_Verify_Init(pk):
     return ctx
 
 
-def ed25519_Verify_Check(ctx, sig, msg):
+def ed25519_Verify_Check_strict(ctx, sig, msg):
+    """ed25519_Verify_Check under the strict rules (rules 2-4 on the context's key bytes 0..31)."""
+    return ed25519_Verify_Check(ctx, sig, msg, strict=True)
+
+
+def ed25519_Verify_Check(ctx, sig, msg, strict=False):
     """One key (a 2080-byte context), n (signature, message) pairs -> int32[n] verdicts."""
     ctx = np.ascontiguousarray(ctx, dtype=np.uint8).reshape(-1)
     if ctx.size != 2080:
@@ -225,8 +241,8 @@ def ed25519_Verify_Check(ctx, sig, msg):
     n = sig.shape[0]
     msg, msg_size = _msgs(msg, n)
     ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_Verify_Check_batch(_ptr(ok), _ptr(ctx), _ptr(sig), _ptr(msg), msg_size, n),
-               "ed25519_Verify_Check_batch")
+    name = "ed25519_Verify_Check_strict_batch" if strict else "ed25519_Verify_Check_batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(ctx), _ptr(sig), _ptr(msg), msg_size, n), name)
     return ok
 
 
@@ -404,10 +420,26 @@ def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):
         _lib.check(_lib.load().ed25519_Verify_Check_indexed_dev(*args, msg.shape[1], n, st), "ed25519_Verify_Check_indexed_dev")
 
 
-def ed25519_VerifySignature_dev(verdict, sig, pk, msg):
+def ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=False):
     import torch
     n, d = sig.shape[0], sig.device
     args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
             _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
+    name = "ed25519_VerifySignature_strict_dev" if strict else "ed25519_VerifySignature_dev"
     with _on(sig) as st:
-        _lib.check(_lib.load().ed25519_VerifySignature_dev(*args, msg.shape[1], n, st), "ed25519_VerifySignature_dev")
+        _lib.check(getattr(_lib.load(), name)(*args, msg.shape[1], n, st), name)
+
+
+def ed25519_VerifySignature_strict_dev(verdict, sig, pk, msg):
+    """Device form of ed25519_VerifySignature_strict: verdict int32[n, 1]."""
+    ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=True)
+
+
+def ed25519_Verify_Check_strict_dev(verdict, ctx, sig, msg):
+    """Device form of ed25519_Verify_Check_strict: ctx uint8[1, 2080] on the device, verdict int32[n, 1]."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(ctx, 2080, "ctx", 1, device=d), _check(sig, 64, "sig"),
+            _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_Verify_Check_strict_dev(*args, msg.shape[1], n, st), "ed25519_Verify_Check_strict_dev")

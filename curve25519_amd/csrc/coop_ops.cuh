@@ -9,6 +9,7 @@
 #include "lanes.cuh"
 #include "verify_fast.cuh"
 #include "coop25519.cuh"
+#include "strict25519.cuh"
 
 namespace c25519 {
 
@@ -26,6 +27,16 @@ struct FastScratch {
 };
 constexpr size_t FAST_TABLE_WORDS = 2 * WTABLE_WORDS;
 constexpr u32 FLAG_R_OK = 1u, FLAG_KEY_OK = 2u, FLAG_FITS = 4u, FLAG_TAU_NEG = 8u, FLAG_SLOW = 16u;
+constexpr u32 FLAG_REJECT = 32u;    // the strict calls only: the element breaks one of the input rules (strict25519.cuh), its verdict is 0
+
+// the strict lattice path's flag decisions, shared by its kernels (engine_verify.hip) and the CPU emulator: rules 1 and 5 in the scalar
+// step; then the key lane of the point step, given its key's verdict on rules 2-4 (ok): a rejected element is also marked FLAG_SLOW,
+// so that the walk skips it, but is put on no list (its verdict is written there and then)
+C25519_DEV u32 strict_pair_flags(const u32 (&Rw)[8], const u32 (&Sw)[8]) { return strict_reject_pair(Rw, Sw) & FLAG_REJECT; }
+C25519_DEV u32 strict_key_flags(u32 f, u32 ok)
+{
+    return (!ok || (f & FLAG_REJECT)) ? FLAG_REJECT | FLAG_SLOW : (f & FLAG_FITS) ? FLAG_KEY_OK : FLAG_KEY_OK | FLAG_SLOW;
+}
 
 namespace coop {
 
@@ -313,6 +324,24 @@ C25519_DEV void verify_check_one(u32* lds, const Lane& L, int* verdict, const vo
     if (threadIdx.x == 0) verdict[e] = diff == 0 ? 1 : 0;
 }
 
+// Rules 2-4 of the strict calls (strict25519.cuh) for the key bytes w, by the whole wave: all-ones iff y < p, y mod p is not the y of a
+// point of small order, and the key decodes onto the curve (calc_x_checked's verdict; the parity asked for does not change it).
+// Every lane returns the same value.  lds: LDS_WORDS words.
+C25519_DEV u32 strict_key_ok(u32* lds, const Lane& L, const u32 (&w)[8])
+{
+    u32 yw[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) yw[i] = w[i];
+    yw[7] &= 0x7fffffffu;
+    fe Y;
+    fe_from_words(Y, yw);
+    setup_one(lds, L);
+    const u32 yl = my_limb(lds, L, Y);
+    u32 xl, x_zero;
+    const u32 on_curve = calc_x_checked(lds, L, xl, x_zero, yl, 0u);
+    return on_curve & ~strict_reject_key(w);
+}
+
 // The whole lattice path of ONE element by a workgroup of THREE waves (k_ed25519_verify_one_per_group):
 //   phase 1   wave 0 hashes and reduces (every lane on the same values) WHILE wave 1 decodes R and wave 2 the key, each square
 //             root by the whole wave (calc_x_checked; they do not need the scalars);
@@ -332,6 +361,9 @@ constexpr int V3_LDS_WORDS = V3_BASE2 + V3_ROWQ2 + SC_ROUNDS * 4 * 64;
 
 // lds_all: V3_LDS_WORDS words; park: 40 words (limbs of the key's x, y and of R's); hand: 4 words (tau < 0; wave 0's flag bits;
 // key on the curve; R decodes canonically)
+// Strict (the strict calls): wave 0 also tests S < L and R's y, wave 2 the key's y; an element that breaks a rule gets verdict 0
+// there and never goes on the slow list.
+template <bool Strict = false>
 C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const FastScratch& fs, int* verdict, const void* sig, const void* pk,
                                    const Msgs& msgs, size_t n, size_t e, const u32* __restrict__ g_tbl)
 {
@@ -351,6 +383,7 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
             const int top = lat_ok ? walk_top_digit(tau, rho) : 0;
             hand[0] = tau_neg;
             hand[1] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8);
+            if (Strict) hand[1] |= strict_pair_flags(Rw, Sw);
         }
     } else {
         // ed_verify_fast_decode (verify_fast.cuh) by a whole wave each: wave 1 takes R -- which must be the canonical encoding of a
@@ -378,6 +411,7 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
         // y < p, and the sign bit an encoder would have produced: x = 0 has parity 0 only
         const u32 canonical = (diff == 0 && !(x_zero && (parity & 1u))) ? 0xffffffffu : 0u;
         ok &= ~is_r | canonical;
+        if (Strict) ok &= is_r | ~strict_reject_key(w);
         const u32 neg = carry_small(L, (u64)(L.p2 - xl));
         if (is_r) xl = neg;
         if (lane == 0) hand[is_r ? 3 : 2] = ok ? 1u : 0u;
@@ -388,6 +422,13 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
     }
     __syncthreads();
     const u32 f = hand[1] | (hand[2] ? FLAG_KEY_OK : 0u) | (hand[3] ? FLAG_R_OK : 0u);
+    if (Strict && ((f & FLAG_REJECT) || !(f & FLAG_KEY_OK))) {             // rules 1-5 (a key off the curve breaks rule 4)
+        if (threadIdx.x == 0) {
+            fs.flags[e] = f | FLAG_REJECT;
+            verdict[e] = 0;
+        }
+        return;
+    }
     if ((f & (FLAG_KEY_OK | FLAG_FITS)) != (FLAG_KEY_OK | FLAG_FITS)) {      // off-curve key / over-long vector: the slow list
         if (threadIdx.x == 0) {
             fs.flags[e] = f | FLAG_SLOW;

@@ -450,16 +450,29 @@ int ed25519_SignMessage_blinded_batch(unsigned char* sig, const unsigned char* p
     return sign_batch(sig, priv, blinding, msg, msg_size, n);
 }
 
-int ed25519_VerifySignature_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
-                                  const unsigned char* msg, size_t msg_size, size_t n)
+static int verify_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msg, size_t msg_size,
+                        size_t n, bool strict)
 {
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ pk, nullptr, 32 }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_VerifySignature_dev(d[3], d[0], d[1], d[2], msg_size, c, st);
+                         return (strict ? ed25519_VerifySignature_strict_dev : ed25519_VerifySignature_dev)(d[3], d[0], d[1], d[2],
+                                                                                                            msg_size, c, st);
                      });
+}
+
+int ed25519_VerifySignature_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                  const unsigned char* msg, size_t msg_size, size_t n)
+{
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, false);
+}
+
+int ed25519_VerifySignature_strict_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                         const unsigned char* msg, size_t msg_size, size_t n)
+{
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, true);
 }
 
 // ragged messages: message i is msgs[offsets[i] .. offsets[i+1]); offsets has n+1 entries (host memory).
@@ -498,8 +511,8 @@ int ed25519_SignMessage_ragged_batch(unsigned char* sig, const unsigned char* pr
     return 0;
 }
 
-int ed25519_VerifySignature_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
-                                         const unsigned char* msgs, const uint64_t* offsets, size_t n)
+static int verify_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msgs,
+                               const uint64_t* offsets, size_t n, bool strict)
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
@@ -515,10 +528,23 @@ int ed25519_VerifySignature_ragged_batch(int* verdict, const unsigned char* sig,
     C25519_RC(t.reserve_dev(L, 2, sizeof(int) * n));
     C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], sig, 64 * n, hipMemcpyHostToDevice, st));
     C25519_TRY(hipMemcpyAsync(t.dbuf[L][1], pk, 32 * n, hipMemcpyHostToDevice, st));
-    C25519_RC(ed25519_VerifySignature_ragged_dev(t.dbuf[L][2], t.dbuf[L][0], t.dbuf[L][1], d_msgs, (const uint64_t*)d_off, n, st));
+    C25519_RC((strict ? ed25519_VerifySignature_strict_ragged_dev : ed25519_VerifySignature_ragged_dev)(
+        t.dbuf[L][2], t.dbuf[L][0], t.dbuf[L][1], d_msgs, (const uint64_t*)d_off, n, st));
     C25519_TRY(hipMemcpyAsync(verdict, t.dbuf[L][2], sizeof(int) * n, hipMemcpyDeviceToHost, st));
     C25519_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+int ed25519_VerifySignature_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                         const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, false);
+}
+
+int ed25519_VerifySignature_strict_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                                const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, true);
 }
 
 // ---- the reference's single-call API: a device batch of one, fatal on device failure --------------
@@ -596,8 +622,8 @@ int ed25519_Verify_Init_batch(void* ctx, const unsigned char* pk, size_t n)
                      });
 }
 
-int ed25519_Verify_Check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
-                               size_t msg_size, size_t n)
+static int verify_check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg, size_t msg_size,
+                              size_t n, bool strict)
 {
     C25519_API_CALL();
     if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
@@ -617,8 +643,20 @@ int ed25519_Verify_Check_batch(int* verdict, const void* ctx, const unsigned cha
     }
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_Verify_Check_dev(d[2], dctx, d[0], d[1], msg_size, c, st);
+                         return (strict ? ed25519_Verify_Check_strict_dev : ed25519_Verify_Check_dev)(d[2], dctx, d[0], d[1], msg_size, c, st);
                      });
+}
+
+int ed25519_Verify_Check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
+                               size_t msg_size, size_t n)
+{
+    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, false);
+}
+
+int ed25519_Verify_Check_strict_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
+                                      size_t msg_size, size_t n)
+{
+    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, true);
 }
 
 // many contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are

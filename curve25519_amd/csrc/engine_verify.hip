@@ -60,7 +60,8 @@ __global__ void __launch_bounds__(ED_BLOCK, C25519_VC_WAVES) k_ed25519_verify_ch
 // Per-element hand-over, struct-of-arrays: sigma_cols[SIGMA_WORDS] (sigma's signed comb columns), rho[5], tau[5] (biased), a flag word
 //   bit 0  R decodes canonically onto the curve      bit 1  the key is on the curve
 //   bit 2  the short vector fits the walk             bit 3  tau < 0
-//   bit 4  the element is on the slow list            bits 8..13  top nonzero digit of the element's scalars
+//   bit 4  the element is on the slow list            bit 5  the element breaks a strict input rule (strict calls only)
+//   bits 8..13  top nonzero digit of the element's scalars
 // (FastScratch, the scratch of the lattice path, and the FLAG_* bits: coop_ops.cuh)
 constexpr int FS_BLOCK = 256;
 #ifndef C25519_VW_WAVES
@@ -77,6 +78,9 @@ constexpr int WALK_BLOCK = C25519_WALK_BLOCK;
 #define C25519_VD_WAVES 3            // ... and the point decoding + table kernel
 #endif
 
+// Strict (the kernels' *_strict twins): rules 1 and 5 here, rules 2-4 in the key lane of the points, which writes verdict 0 for a
+// rejected element and marks it FLAG_REJECT | FLAG_SLOW: the plain walk skips it, and it goes on no list
+template <bool Strict = false>
 C25519_DEV void verify_scalars_lane(const FastScratch& fs, const void* sig, const void* pk, const Msgs& msgs, size_t n, size_t i)
 {
     u32 pkw[8], Rw[8], Sw[8], cols[SIGMA_WORDS], rho[5], tau[5], tau_neg;
@@ -89,24 +93,41 @@ C25519_DEV void verify_scalars_lane(const FastScratch& fs, const void* sig, cons
 #pragma unroll
     for (int w = 0; w < 5; w++) { fs.rho[(size_t)w * n + i] = rho[w]; fs.tau[(size_t)w * n + i] = tau[w]; }
     const int top = lat_ok ? walk_top_digit(tau, rho) : 0;
-    fs.flags[i] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8);
+    if (Strict) {                                            // R and S again from L2: kept across the hash they cost a wave per SIMD
+        load32(Rw, sig, 2 * i);
+        load32(Sw, sig, 2 * i + 1);
+        fs.flags[i] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8) | strict_pair_flags(Rw, Sw);
+    } else
+        fs.flags[i] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8);
 }
 
 
 // step 1: hash, short lattice vector, sigma -- integer work only
-__global__ void __launch_bounds__(FS_BLOCK) k_ed25519_verify_fast_scalars(FastScratch fs, const void* sig, const void* pk,
-                                                                          Msgs msgs, size_t n)
+template <bool Strict>
+C25519_DEV void verify_fast_scalars(const FastScratch& fs, const void* sig, const void* pk, const Msgs& msgs, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * FS_BLOCK + threadIdx.x;
     if (i == 0) fs.slow_count[0] = fs.slow_count[1] = fs.slow_count[2] = 0;
     if (i >= n) return;
-    verify_scalars_lane(fs, sig, pk, msgs, n, i);
+    verify_scalars_lane<Strict>(fs, sig, pk, msgs, n, i);
+}
+
+__global__ void __launch_bounds__(FS_BLOCK) k_ed25519_verify_fast_scalars(FastScratch fs, const void* sig, const void* pk,
+                                                                          Msgs msgs, size_t n)
+{
+    verify_fast_scalars<false>(fs, sig, pk, msgs, n);
+}
+
+__global__ void __launch_bounds__(FS_BLOCK) k_ed25519_verify_fast_scalars_strict(FastScratch fs, const void* sig, const void* pk,
+                                                                                 Msgs msgs, size_t n)
+{
+    verify_fast_scalars<true>(fs, sig, pk, msgs, n);
 }
 
 // step 2: the two points of an element, one per lane: lane j < n decodes key j, lane n + j decodes R of signature j (a
 // square root each), then builds that point's window table.  2n lanes, 168 registers: three waves per SIMD, no spills.
-__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fast_points(FastScratch fs, const void* sig, const void* pk,
-                                                                                          size_t n)
+template <bool Strict>
+C25519_DEV void verify_fast_points(FastScratch fs, const void* sig, const void* pk, size_t n, int* verdict)
 {
     const size_t j = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
     if (j >= 2 * n) return;
@@ -117,7 +138,7 @@ __global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fa
     const u32 f = fs.flags[e];
     const u32 tau_neg = (f & FLAG_TAU_NEG) ? 0xffffffffu : 0u;
     fe X, Y;
-    const u32 ok = ed_verify_fast_decode(X, Y, w, is_r ? 0xffffffffu : 0u, tau_neg);
+    const u32 ok = ed_verify_fast_decode(X, Y, w, is_r ? 0xffffffffu : 0u, tau_neg) & (Strict && !is_r ? ~strict_reject_key(w) : 0xffffffffu);
 #if C25519_WALK_SORTED
     if (!is_r) {                                                   // the walk's order (see FastScratch::order)
         const bool is_long = ((f >> 8) & 63u) > 32u;
@@ -127,6 +148,13 @@ __global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fa
 #endif
     if (is_r) {
         if (ok) atomicOr(&fs.flags[e], FLAG_R_OK);
+    } else if (Strict) {
+        // strict_key_flags (coop_ops.cuh): a rejected element is marked as listed, so that the plain walk skips it, but goes on no list;
+        // its verdict is written here
+        const u32 add = strict_key_flags(f, ok);
+        atomicOr(&fs.flags[e], add);
+        if (add & FLAG_REJECT) verdict[e] = 0;
+        else if (add & FLAG_SLOW) fs.slow_list[atomicAdd(fs.slow_count, 1u)] = (u32)e;
     } else if (ok && (f & FLAG_FITS)) {
         atomicOr(&fs.flags[e], FLAG_KEY_OK);
     } else {                                                      // an element the walk cannot decide: on the slow list
@@ -139,6 +167,18 @@ __global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fa
     // profiles/r03_ab_verify_structure.txt).
     // (An element that turns out to be on the slow list gets tables nobody reads: the key lane cannot tell the R lane in time.)
     wtable_build(fs.tables + e * FAST_TABLE_WORDS + (is_r ? WTABLE_WORDS : 0), X, Y);
+}
+
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fast_points(FastScratch fs, const void* sig, const void* pk,
+                                                                                          size_t n)
+{
+    verify_fast_points<false>(fs, sig, pk, n, nullptr);
+}
+
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fast_points_strict(FastScratch fs, const void* sig,
+                                                                                                 const void* pk, size_t n, int* verdict)
+{
+    verify_fast_points<true>(fs, sig, pk, n, verdict);
 }
 
 // step 3: the walk and the neutral-element test (ge_walk_is_neutral).  Beside the accumulator point only the round's two
@@ -189,6 +229,9 @@ __global__ void __launch_bounds__(WALK_BLOCK, C25519_VW_WAVES) k_ed25519_verify_
 //    in two product levels and a doubling in a level of squarings and one of products (~2.3 x shorter than a lane's); it also
 //    makes the slow list (an element the walk cannot decide: off-curve key, over-long vector) for step 5 behind it.  64 elements
 //    (four waves) per workgroup share one staged comb table; element order (no long / short sorting: 16 elements per wave).
+//  * Strict (the *_strict twins): the scalar lanes apply rules 1 and 5, a key lane rules 2-4 (its pflags word is then zero); the walk
+//    writes verdict 0 for an element that breaks one, and lists it nowhere.  The two twins are written out: as templates of the plain
+//    kernels they changed the plain kernels' gfx950 code (instruction order), which must stay what it was.
 __global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_quad_prep(FastScratch fs, const void* sig, const void* pk,
                                                                                          Msgs msgs, size_t n, unsigned scalar_blocks)
 {
@@ -208,6 +251,28 @@ __global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_qu
     if (is_r) load32(w, sig, 2 * e); else load32(w, pk, e);
     fe X, Y;
     const u32 ok = ed_verify_fast_decode(X, Y, w, is_r ? 0xffffffffu : 0u, 0u);
+    fs.pflags[j] = ok;
+    wtable_build(fs.tables + e * FAST_TABLE_WORDS + (is_r ? WTABLE_WORDS : 0), X, Y);
+}
+
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_quad_prep_strict(FastScratch fs, const void* sig, const void* pk,
+                                                                                                Msgs msgs, size_t n, unsigned scalar_blocks)
+{
+    if (blockIdx.x < scalar_blocks) {
+        const size_t i = (size_t)blockIdx.x * FS_BLOCK + threadIdx.x;
+        if (i == 0) fs.slow_count[0] = fs.slow_count[1] = fs.slow_count[2] = 0;
+        if (i >= n) return;
+        verify_scalars_lane<true>(fs, sig, pk, msgs, n, i);
+        return;
+    }
+    const size_t j = (size_t)(blockIdx.x - scalar_blocks) * ED_BLOCK + threadIdx.x;
+    if (j >= 2 * n) return;
+    const bool is_r = j >= n;
+    const size_t e = is_r ? j - n : j;
+    u32 w[8];
+    if (is_r) load32(w, sig, 2 * e); else load32(w, pk, e);
+    fe X, Y;
+    const u32 ok = ed_verify_fast_decode(X, Y, w, is_r ? 0xffffffffu : 0u, 0u) & (is_r ? 0xffffffffu : ~strict_reject_key(w));
     fs.pflags[j] = ok;
     wtable_build(fs.tables + e * FAST_TABLE_WORDS + (is_r ? WTABLE_WORDS : 0), X, Y);
 }
@@ -241,6 +306,37 @@ k_ed25519_verify_quad_walk(FastScratch fs, int* verdict, size_t n, const u32* __
     if (R.is0) verdict[i] = (neutral & r_ok) ? 1 : 0;
 }
 
+// ... the strict twin (a key that breaks rules 2-4 has pflags 0: it is rejected, not listed)
+__global__ void __launch_bounds__(QW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2)))
+k_ed25519_verify_quad_walk_strict(FastScratch fs, int* verdict, size_t n, const u32* __restrict__ g_tbl)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds_tbl[SC_TBL_WORDS];
+    lds_stage_words(lds_tbl, g_tbl + SC_TBL_OFFSET, SC_TBL_WORDS);
+    const size_t i = (size_t)blockIdx.x * (QW_BLOCK / 4) + (threadIdx.x >> 2);
+    const u32 f = i < n ? fs.flags[i] : 0u;
+    const u32 key_ok = i < n ? fs.pflags[i] : 0u, r_ok = i < n ? fs.pflags[n + i] : 0u;
+    const bool rejected = i < n && ((f & FLAG_REJECT) || !key_ok);
+    const bool walks = !rejected && (f & FLAG_FITS);
+    int top = walks ? (int)((f >> 8) & 63u) : 0;           // the wave walks from its longest element's first digit
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int other = __shfl_xor(top, o);
+        top = other > top ? other : top;
+    }
+    top = __builtin_amdgcn_readfirstlane(top);
+    const quad::Roles R = quad::roles();
+    if (!walks) {                                         // (whole quads leave)
+        if (rejected && R.is0) verdict[i] = 0;
+        else if (i < n && R.is0) fs.slow_list[atomicAdd(fs.slow_count, 1u)] = (u32)i;
+        return;
+    }
+    const u32* tq = fs.tables + i * FAST_TABLE_WORDS;
+    const WalkScalars sc{ fs.sigma, fs.tau, fs.rho, n, i };
+    const u32 q_flip = (f & FLAG_TAU_NEG) ? 0xffffffffu : 0u;
+    const u32 neutral = quad::walk_is_neutral(sc, tq, tq + WTABLE_WORDS, lds_tbl, top < 8 ? 8 : top, R, q_flip);
+    if (R.is0) verdict[i] = (neutral & r_ok) ? 1 : 0;
+}
+
 // The whole lattice path of ONE element in ONE launch, for a call of a few elements: a workgroup of THREE waves per element
 // (coop::verify_three_waves, coop_ops.cuh: wave 0 hashes and reduces while wave 1 takes the two square roots; then the three
 // products of sigma*B + tau*Q + rho*(-R) = O side by side, a wave each; wave 0 adds and tests).  Three launches ran
@@ -254,6 +350,16 @@ k_ed25519_verify_one_per_group(FastScratch fs, int* verdict, const void* sig, co
     __shared__ u32 park[40], hand[4];
     if (blockIdx.x >= n) return;
     coop::verify_three_waves(lds_all, park, hand, fs, verdict, sig, pk, msgs, n, blockIdx.x, g_tbl);
+}
+
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 2)))
+k_ed25519_verify_one_per_group_strict(FastScratch fs, int* verdict, const void* sig, const void* pk, Msgs msgs, size_t n,
+                                      const u32* __restrict__ g_tbl)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds_all[coop::V3_LDS_WORDS];
+    __shared__ u32 park[40], hand[4];
+    if (blockIdx.x >= n) return;
+    coop::verify_three_waves<true>(lds_all, park, hand, fs, verdict, sig, pk, msgs, n, blockIdx.x, g_tbl);
 }
 
 // step 5: the elements on the slow list (off-curve keys -- the reference does not reject them, so neither may we -- and
@@ -538,6 +644,34 @@ k_ed25519_verify_check_indexed_coop(int* verdict, const void* sig, const u32* __
     if (threadIdx.x == 0) signal_done(done);
 }
 
+// ---- ed25519_Verify_Check_strict_*: one kernel behind the plain call's ---------------------------------------------------------
+// The plain kernels decide rule 6; this one applies the others to their verdicts.  Every workgroup decides rules 2-4 for the context's
+// key bytes itself -- its first wave takes the square root cooperatively (coop::strict_key_ok) -- so no word is handed from kernel to
+// kernel; the grid stops at SM_MAX_BLOCKS workgroups (one square root per SIMD at most) and strides over the pairs, applying rules 1
+// and 5 per pair.  Element 0's lane signals a call of one.
+constexpr int SM_BLOCK = 256, SM_MAX_BLOCKS = 1024;
+__global__ void __launch_bounds__(SM_BLOCK) k_ed25519_verify_check_strict_mask(int* verdict, const void* sig, size_t n,
+                                                                               const u32* __restrict__ ctx, DoneWord done)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[coop::LDS_WORDS];
+    __shared__ u32 key_ok;
+    if (threadIdx.x < 64) {
+        u32 w[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = ctx[j];
+        const u32 ok = coop::strict_key_ok(lds, coop::make_lane(threadIdx.x), w);
+        if (threadIdx.x == 0) key_ok = ok;
+    }
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * SM_BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * SM_BLOCK) {
+        u32 Rw[8], Sw[8];
+        load32(Rw, sig, 2 * i);
+        load32(Sw, sig, 2 * i + 1);
+        if (!key_ok || strict_reject_pair(Rw, Sw)) verdict[i] = 0;
+        if (i == 0) signal_done(done);                     // (done: a call of ONE pair, this lane's own store in front of it)
+    }
+}
+
 namespace {
 
 // scratch of one verification pass: per-lane tables (the larger of the two paths' formats: they never live at the same
@@ -564,8 +698,10 @@ thread_local LastVerify tl_last_verify;
 struct LastCheck { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
 thread_local LastCheck tl_last_check;
 
+// strict (fast only): the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh)
 template <typename MakeFin>
-int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin)
+int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin,
+               bool strict = false)
 {
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
@@ -595,20 +731,27 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
         }
         if (!verify_quad_for(n) && verify_coop_for(n)) {   // a few elements: one launch, three waves per element
             C25519_TRY(hipMemsetAsync(fs.slow_count, 0, 3 * sizeof(u32), stream));
-            k_ed25519_verify_one_per_group<<<(unsigned)n, 192, 0, stream>>>(fs, verdict, sig, pk, msgs, n, tbl);
+            (strict ? k_ed25519_verify_one_per_group_strict : k_ed25519_verify_one_per_group)<<<(unsigned)n, 192, 0, stream>>>(
+                fs, verdict, sig, pk, msgs, n, tbl);
             C25519_TRY(hipGetLastError());
         } else if (verify_quad_for(n)) {                   // four lanes per element walk; scalars and points side by side in one launch
             const unsigned sb = grid_for(n, FS_BLOCK);
-            k_ed25519_verify_quad_prep<<<sb + grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, msgs, n, sb);
+            (strict ? k_ed25519_verify_quad_prep_strict : k_ed25519_verify_quad_prep)<<<sb + grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
+                fs, sig, pk, msgs, n, sb);
             C25519_TRY(hipGetLastError());
-            k_ed25519_verify_quad_walk<<<grid_for(n, QW_BLOCK / 4), QW_BLOCK, 0, stream>>>(fs, verdict, n, tbl);
+            (strict ? k_ed25519_verify_quad_walk_strict : k_ed25519_verify_quad_walk)<<<grid_for(n, QW_BLOCK / 4), QW_BLOCK, 0, stream>>>(
+                fs, verdict, n, tbl);
             C25519_TRY(hipGetLastError());
         } else {
-            k_ed25519_verify_fast_scalars<<<grid_for(n, FS_BLOCK), FS_BLOCK, 0, stream>>>(fs, sig, pk, msgs, n);
+            (strict ? k_ed25519_verify_fast_scalars_strict : k_ed25519_verify_fast_scalars)<<<grid_for(n, FS_BLOCK), FS_BLOCK, 0, stream>>>(
+                fs, sig, pk, msgs, n);
             C25519_TRY(hipGetLastError());
-            k_ed25519_verify_fast_points<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n);
+            if (strict)
+                k_ed25519_verify_fast_points_strict<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n, verdict);
+            else
+                k_ed25519_verify_fast_points<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n);
             C25519_TRY(hipGetLastError());
-            k_ed25519_verify_fast_walk<<<grid_for(n, WALK_BLOCK), WALK_BLOCK, 0, stream>>>(fs, verdict, n, tbl);
+            k_ed25519_verify_fast_walk<<<grid_for(n, WALK_BLOCK), WALK_BLOCK, 0, stream>>>(fs, verdict, n, tbl);   // (strict: rejected = listed)
             C25519_TRY(hipGetLastError());
         }
         k_ed25519_verify_slow<<<grid, ED_BLOCK, 0, stream>>>(fs, verdict, sig, pk, msgs, tbl, take_done_word(n));
@@ -633,15 +776,16 @@ extern "C" {
 
 size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return verify_scratch_bytes(n); }
 
-static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream)
+static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, bool strict = false)
 {
     // tunable VERIFY_REFERENCE_ORDER = 1: every element through the reference-order kernels -- Verify_Init's 4-fold table per
-    // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob)
-    const bool fast = c25519_host::tunable_or(c25519_host::T_VERIFY_REFERENCE_ORDER, 0) == 0;
+    // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob).
+    // The strict calls always take the lattice path: their rules live in its kernels.
+    const bool fast = strict || c25519_host::tunable_or(c25519_host::T_VERIFY_REFERENCE_ORDER, 0) == 0;
     if (int rc = check_dev_args(n, { verdict, sig, pk })) return rc;
     if (n == 0) return 0;
     return verify_run(sig, pk, msgs, n, stream, (int*)verdict, fast,
-                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; });
+                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, strict);
 }
 
 // test hook: enc(T) instead of the verdict (what Verify_Check compares with enc(R)); device pointers
@@ -686,6 +830,23 @@ int ed25519_VerifySignature_ragged_dev(void* verdict, const void* sig, const voi
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
     return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
                       (hipStream_t)stream);
+}
+
+int ed25519_VerifySignature_strict_dev(void* verdict, const void* sig, const void* pk, const void* msg, size_t msg_size,
+                                       size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
+    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, true);
+}
+
+int ed25519_VerifySignature_strict_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
+                                              const uint64_t* offsets, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
+    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
+                      (hipStream_t)stream, true);
 }
 
 // two-phase verification on the device: contexts are 2080-byte records (pk || 16 x 128-byte canonical rows),
@@ -780,6 +941,23 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
     C25519_RC(keep_lease.release());
     return lease.release();
+}
+
+// ed25519_Verify_Check_dev under the strict rules: the plain call, then k_ed25519_verify_check_strict_mask on the same stream
+int ed25519_Verify_Check_strict_dev(void* verdict, const void* ctx, const void* sig, const void* msg, size_t msg_size,
+                                    size_t n, void* stream_)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
+    if (n == 0) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    const DoneWord done = take_done_word(n);               // the mask kernel's, so that the plain kernels find none to signal
+    C25519_RC(ed25519_Verify_Check_dev(verdict, ctx, sig, msg, msg_size, n, stream_));
+    const unsigned grid = grid_for(n, SM_BLOCK) < SM_MAX_BLOCKS ? grid_for(n, SM_BLOCK) : SM_MAX_BLOCKS;
+    k_ed25519_verify_check_strict_mask<<<grid, SM_BLOCK, 0, stream>>>((int*)verdict, sig, n, (const u32*)ctx, done);
+    C25519_TRY(hipGetLastError());
+    return 0;
 }
 
 // n x ed25519_Verify_Check(ctxs + 2080 * ctx_index[i], pair i): up to COOP_MAX pairs (default 1024) one per wave, above that one per

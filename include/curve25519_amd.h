@@ -235,6 +235,33 @@ int ed25519_VerifySignature_ragged_batch(int *verdict, const unsigned char *sig,
 int ed25519_VerifySignature_ragged_dev(void *verdict, const void *sig, const void *pk, const void *msgs,
                                        const uint64_t *offsets, size_t n, void *stream);
 
+/* Strict verification: the verdict of libsodium 1.0.18's crypto_sign_verify_detached (default build), which rejects the
+ * malleable and degenerate inputs the reference accepts.  Read S = sig[32..63], y_R = sig[0..31] and y_A = pk as little-endian
+ * integers, bit 255 cleared from y_R and y_A; Y_small = {0, 1, p - 1, y8, p - y8}, y8 the y of a point of order 8.  The
+ * verdict is 1 exactly when
+ *   1. S < L;
+ *   2. y_A < p (a canonical key);
+ *   3. y_A mod p is not in Y_small (no key of small order);
+ *   4. the key decodes onto the curve;
+ *   5. y_R mod p is not in Y_small, over all 255-bit values (so p and p + 1 count);
+ *   6. the plain call's verdict is 1 (cofactorless: enc(S*B - h*A) equals R byte for byte).
+ * Mixed-order keys a*B + T are accepted when the signature is right, as in libsodium.
+ *   Plain calls (ed25519_VerifySignature_*, the reference): rule 6 only -- (R, S + L) verifies wherever (R, S) does, and keys and
+ *   R of small order, non-canonical keys and keys off the curve are taken as they are.
+ *   OpenSSL 3.0 (EVP_DigestVerify, 3.0.2): rules 1, 4 and 6; it accepts keys and R of small order and keys with y >= p.
+ * The rules are decided inside the lattice path's kernels (csrc/strict25519.cuh): an element that breaks one gets verdict 0
+ * there and never goes to the reference-order kernel, so a key off the curve costs no more than an honest one
+ * (c25519_amd_verify_last_slow_elements reports 0 for it).  The tunable VERIFY_REFERENCE_ORDER does not apply.  Argument
+ * rules, dispatch and the other tunables are ed25519_VerifySignature_*'s. */
+int ed25519_VerifySignature_strict_batch(int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                         const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_VerifySignature_strict_dev(void *verdict, const void *sig, const void *pk, const void *msg,
+                                       size_t msg_size, size_t n, void *stream);
+int ed25519_VerifySignature_strict_ragged_batch(int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                                const unsigned char *msgs, const uint64_t *offsets, size_t n);
+int ed25519_VerifySignature_strict_ragged_dev(void *verdict, const void *sig, const void *pk, const void *msgs,
+                                              const uint64_t *offsets, size_t n, void *stream);
+
 /* ed25519_VerifySignature_* decide every element whose key decompresses onto the curve with an exact
  * lattice-shortened walk (csrc/verify_fast.cuh, ~134 doublings instead of 255) and run the reference's own operation
  * order only for the others (set C25519_AMD_VERIFY_REFERENCE_ORDER=1 to force it for everything).  This reports how many
@@ -268,6 +295,13 @@ int ed25519_Verify_Check_batch(int *verdict, const void *ctx, const unsigned cha
                                const unsigned char *msg, size_t msg_size, size_t n);
 int ed25519_Verify_Check_dev(void *verdict, const void *ctx, const void *sig, const void *msg,
                              size_t msg_size, size_t n, void *stream);
+/* ed25519_Verify_Check_* under the strict rules 1-6 (above ed25519_VerifySignature_strict_batch): rules 2-4 apply to the context's
+ * key bytes 0..31; rule 6 is ed25519_Verify_Check_*'s verdict, whose kernels read the rows as they are.  One kernel behind those
+ * applies rules 1-5 (each of its workgroups decides the key itself): it adds 26-46 us per call (profiles/verify_strict_rate.txt). */
+int ed25519_Verify_Check_strict_batch(int *verdict, const void *ctx, const unsigned char *sig,
+                                      const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_Verify_Check_strict_dev(void *verdict, const void *ctx, const void *sig, const void *msg,
+                                    size_t msg_size, size_t n, void *stream);
 /* n x ed25519_Verify_Check(ctxs + 2080 * ctx_index[i], sig_i, msg_i): MANY contexts in one call, a mixed stream of
  * (context, signature, message) triples in any order.  ctxs holds n_ctx records of 2080 bytes (Verify_Init's layout, read as
  * they are, like the reference: element i's verdict is what ed25519_Verify_Check_* gives for its context, tampered or not),
