@@ -1,13 +1,9 @@
 // curve25519_amd/csrc/batch_invert.cuh -- what the shared inversion (k_batch_invert, engine_common.cuh; Montgomery's trick over K
-// elements per lane, one inversion per quad of lanes) is made of, in a header that tests/host_emul compiles too: its group sizes, the
+// elements per lane, one inversion per quad of lanes: one per lane lost, profiles/r06_ab_inv_quad.txt) is made of, in a header that tests/host_emul compiles too: its group sizes, the
 // zero swap, the LDS moves and the self-test's output.  The lane's work itself is batch_invert_lane.inc (see there why).
 #pragma once
 #include "lanes.cuh"
 #include "quad25519.cuh"
-
-#ifndef C25519_INV_QUAD
-#define C25519_INV_QUAD 1            // A/B switch: 0 = every lane of k_batch_invert inverts its own product (profiles/r06_ab_inv_quad.txt)
-#endif
 
 namespace c25519 {
 

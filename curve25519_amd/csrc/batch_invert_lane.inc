@@ -33,7 +33,6 @@
     // (fe_invert_quad: the division steps' three pairs on three lanes, ~7 700 instructions instead of one lane's ~13 700), then
     // each lane's own 1 / acc = (1 / T) * (the other pair's product) * (its partner's product)
     fe inv;
-#if C25519_INV_QUAD
     {
         fe partner, pair, other_pair, total;
         quad::fe_qperm<1, 0, 3, 2>(partner, acc);
@@ -44,9 +43,6 @@
         fe_mul(inv, inv, other_pair);
         fe_mul(inv, inv, partner);
     }
-#else
-    fe_invert(inv, acc);
-#endif
 #pragma unroll
     for (int t = K - 1; t >= 0; t--) {
         const size_t e = j + (size_t)t * m;

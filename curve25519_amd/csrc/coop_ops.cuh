@@ -86,9 +86,7 @@ C25519_DEV void x25519_one(u32* lds, const Lane& L, void* out, const void* pk, v
         for (int b = top; b >= bottom; b--) {
             const u32 bit = kw >> 31;
             kw <<= 1;
-#ifndef C25519_COOP_SKIP_LADDER                           // timing experiments only (tools/build_variants.sh): wrong results
             v = ladder_step<BASE9>(lds, L, v, (u32)0 - (u32)(bit == prev));
-#endif
             prev = bit;
         }
     }
@@ -100,11 +98,7 @@ C25519_DEV void x25519_one(u32* lds, const Lane& L, void* out, const void* pk, v
 #pragma unroll 1
     for (int i = 0; i < 3; i++) p = mont_double(lds, L, p);
     // x / z: the odd rows' inverse times the even rows' x, in every row; canonical bytes by every lane
-#ifndef C25519_COOP_SKIP_INVERT
     const u32 zi = invert(lds, L, p);
-#else
-    const u32 zi = p;
-#endif
     u32 px, pz, ix, iz;
     pair_exchange(px, pz, p);
     pair_exchange(ix, iz, zi);

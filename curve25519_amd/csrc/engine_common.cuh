@@ -146,7 +146,7 @@ struct FinishVerify {                        // verdict = (enc(T) == enc(R) byte
     }
 };
 
-// (INV_BLOCK, INV_MAX_K, C25519_INV_QUAD: batch_invert.cuh; the lane's work: batch_invert_lane.inc)
+// (INV_BLOCK, INV_MAX_K: batch_invert.cuh; the lane's work: batch_invert_lane.inc)
 // K is a compile-time constant and the loops are unrolled: a lane's K elements live in registers (a lone wave per SIMD has
 // the whole register file: 64-thread workgroups, no occupancy to protect), so the loads of all K elements are issued up
 // front instead of one dependent round trip per element and per pass.  The K - 1 prefix products a lane needs again on

@@ -71,9 +71,6 @@ constexpr int FS_BLOCK = 256;
 #define C25519_WALK_BLOCK C25519_ED_BLOCK       // lanes per walk workgroup (they share one staged comb table)
 #endif
 constexpr int WALK_BLOCK = C25519_WALK_BLOCK;
-#ifndef C25519_WALK_SORTED
-#define C25519_WALK_SORTED 1         // A/B switch: 0 = the walk's lane j takes element j
-#endif
 #ifndef C25519_VD_WAVES
 #define C25519_VD_WAVES 3            // ... and the point decoding + table kernel
 #endif
@@ -139,13 +136,11 @@ C25519_DEV void verify_fast_points(FastScratch fs, const void* sig, const void* 
     const u32 tau_neg = (f & FLAG_TAU_NEG) ? 0xffffffffu : 0u;
     fe X, Y;
     const u32 ok = ed_verify_fast_decode(X, Y, w, is_r ? 0xffffffffu : 0u, tau_neg) & (Strict && !is_r ? ~strict_reject_key(w) : 0xffffffffu);
-#if C25519_WALK_SORTED
     if (!is_r) {                                                   // the walk's order (see FastScratch::order)
         const bool is_long = ((f >> 8) & 63u) > 32u;
         const u32 pos = is_long ? (u32)n - 1u - atomicAdd(fs.slow_count + 2, 1u) : atomicAdd(fs.slow_count + 1, 1u);
         fs.order[pos] = (u32)e;
     }
-#endif
     if (is_r) {
         if (ok) atomicOr(&fs.flags[e], FLAG_R_OK);
     } else if (Strict) {
@@ -193,11 +188,7 @@ __global__ void __launch_bounds__(WALK_BLOCK, C25519_VW_WAVES) k_ed25519_verify_
     __shared__ __attribute__((aligned(16))) u32 lds_tbl[SC_TBL_WORDS];
     lds_stage_words(lds_tbl, g_tbl + SC_TBL_OFFSET, SC_TBL_WORDS);
     const size_t lane = (size_t)blockIdx.x * WALK_BLOCK + threadIdx.x;
-#if C25519_WALK_SORTED
-    const size_t i = lane < n ? fs.order[lane] : n;
-#else
-    const size_t i = lane;
-#endif
+    const size_t i = lane < n ? fs.order[lane] : n;      // (lane j taking element j lost: profiles/r03_ab_verify_structure.txt block 14)
     const u32 f = i < n ? fs.flags[i] : FLAG_SLOW;
     const bool walks = !(f & FLAG_SLOW);
     // the wave walks from its longest element's first digit (the others' digits above their own are zero)
@@ -209,11 +200,7 @@ __global__ void __launch_bounds__(WALK_BLOCK, C25519_VW_WAVES) k_ed25519_verify_
     }
     top = __builtin_amdgcn_readfirstlane(top);           // wave-uniform by construction: let the walk's loops be scalar ones
     if (!walks) return;
-#ifdef C25519_WALK_TABLE_ALIAS                           // TIMING ONLY (wrong verdicts): every element reads one of 1024 tables, L2-resident
-    const u32* tq = fs.tables + (i & 1023) * FAST_TABLE_WORDS;
-#else
     const u32* tq = fs.tables + i * FAST_TABLE_WORDS;
-#endif
     const WalkScalars sc{ fs.sigma, fs.tau, fs.rho, n, i };
     const u32 neutral = ge_walk_is_neutral(sc, tq, tq + WTABLE_WORDS, lds_tbl, top < 8 ? 8 : top);
     verdict[i] = (neutral & f & FLAG_R_OK) ? 1 : 0;

@@ -115,7 +115,6 @@ __global__ void __launch_bounds__(BLOCK, C25519_XF_WAVES) k_x25519_fused(void* o
             if (t < K - 1) lds_put_fe(pbuf + t * 640, 64, tid, acc);
         }
         fe inv;
-#if C25519_INV_QUAD
         {   // one inversion per quad of the wave's lanes (k_batch_invert's exchange, engine_common.cuh)
             fe partner, pair, other_pair, total;
             quad::fe_qperm<1, 0, 3, 2>(partner, acc);
@@ -126,9 +125,6 @@ __global__ void __launch_bounds__(BLOCK, C25519_XF_WAVES) k_x25519_fused(void* o
             fe_mul(inv, inv, other_pair);
             fe_mul(inv, inv, partner);
         }
-#else
-        fe_invert(inv, acc);
-#endif
 #pragma unroll 1
         for (int t = K - 1; t >= 0; t--) {
             fe zi;

@@ -38,29 +38,8 @@ constexpr u32 M25 = 0x1ffffffu;
 
 struct fe { u32 v[10]; };
 
-// A/B knob: the limb mask behind each product column at low wave priority too (valu_gfx950.cuh: C25519_VOP2_RUN_*)
-// every field addition / subtraction / negation / select is such a run (A/B knob C25519_FE_PRIO, default on); the operand
-// doublings at the head of a product too (C25519_MASK_PRIO >= 1)
-#ifndef C25519_FE_PRIO
-#define C25519_FE_PRIO 1
-#endif
-#if C25519_FE_PRIO
-#define C25519_FE_RUN_BEGIN() C25519_VOP2_RUN_BEGIN()
-#define C25519_FE_RUN_END() C25519_VOP2_RUN_END()
-#else
-#define C25519_FE_RUN_BEGIN() do { } while (0)
-#define C25519_FE_RUN_END() do { } while (0)
-#endif
-#ifndef C25519_MASK_PRIO
-#define C25519_MASK_PRIO 1
-#endif
-#if defined(C25519_MASK_PRIO) && C25519_MASK_PRIO
-#define C25519_MASK_RUN_BEGIN() C25519_VOP2_RUN_BEGIN()
-#define C25519_MASK_RUN_END() C25519_VOP2_RUN_END()
-#else
-#define C25519_MASK_RUN_BEGIN() do { } while (0)
-#define C25519_MASK_RUN_END() do { } while (0)
-#endif
+// Every field addition / subtraction / negation / select is a low-priority run of VOP2 instructions (valu_gfx950.cuh:
+// C25519_VOP2_RUN_*), and so are the operand doublings at the head of the ladder's products (profiles/r04_ab_prio.txt)
 
 C25519_DEV constexpr int fe_w(int i) { return (i & 1) ? 25 : 26; }
 C25519_DEV constexpr u32 fe_mask(int i) { return (i & 1) ? M25 : M26; }
@@ -76,45 +55,43 @@ C25519_DEV void fe_set_u32(fe& r, u32 x)
 
 C25519_DEV void fe_add(fe& r, const fe& a, const fe& b)
 {
-    C25519_FE_RUN_BEGIN();
+    C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 0; i < 10; i++) r.v[i] = a.v[i] + b.v[i];
-    C25519_FE_RUN_END();
+    C25519_VOP2_RUN_END();
 }
 
 // r = a - b + 2p  (b must be reduced so that no limb goes negative)
 C25519_DEV void fe_sub(fe& r, const fe& a, const fe& b)
 {
-    C25519_FE_RUN_BEGIN();
+    C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 0; i < 10; i++) r.v[i] = a.v[i] + fe_2p(i) - b.v[i];
-    C25519_FE_RUN_END();
+    C25519_VOP2_RUN_END();
 }
 
 // r = 2p - a   (the reference negates with _w_maxP - A, ed25519_sign.c:130)
 C25519_DEV void fe_neg(fe& r, const fe& a)
 {
-    C25519_FE_RUN_BEGIN();
+    C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 0; i < 10; i++) r.v[i] = fe_2p(i) - a.v[i];
-    C25519_FE_RUN_END();
+    C25519_VOP2_RUN_END();
 }
 
 // branch-free select: r = mask ? a : b, mask is all-ones or zero
 C25519_DEV void fe_select(fe& r, u32 mask, const fe& a, const fe& b)
 {
-    C25519_FE_RUN_BEGIN();
+    C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 0; i < 10; i++) r.v[i] = (a.v[i] & mask) | (b.v[i] & ~mask);
-    C25519_FE_RUN_END();
+    C25519_VOP2_RUN_END();
 }
 
-// limbs l[0..9] hold the masked columns, `carry` is what left column 9: fold it back times 19
+// limbs l[0..9] hold the masked columns, `carry` is what left column 9: fold it back times 19  (a fence behind every product
+// lost: profiles/r03_ab_x25519.txt)
 C25519_DEV void fe_finish_chain(fe& r, u32 (&l)[10], u64 carry)
 {
-#ifdef C25519_FENCE_FIELD                 // A/B knob (profiles/r03_ab_fence.txt): a fence behind every product
-    C25519_SCHED_FENCE();
-#endif
     const u64 t = carry * 19 + l[0];                      // one v_mad_u64_u32
     C25519_COUNT_MAD(1);
     l[0] = (u32)t & M26;
@@ -125,19 +102,16 @@ C25519_DEV void fe_finish_chain(fe& r, u32 (&l)[10], u64 carry)
 
 // RUNS: the operand doublings as a low-priority run and a priority dip behind every column (C25519_VOP2_RUN_*): worth
 // 1.7 % on the X25519 ladder at four waves per SIMD, costs 1.7 % in the verification walk at two (profiles/r04_ab_prio.txt)
-#ifndef C25519_DIP_EVERY
-#define C25519_DIP_EVERY 1                 // A/B knob: a dip behind every n-th column of a product with RUNS
-#endif
 template <bool RUNS = false>
 C25519_DEV void fe_mul_chained(fe& r, const fe& a, const fe& b)
 {
     u32 b19[10], a2[10], l[10];
 #pragma unroll
     for (int j = 1; j < 10; j++) b19[j] = b.v[j] * 19u;
-    if (RUNS) C25519_MASK_RUN_BEGIN();
+    if (RUNS) C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 1; i < 10; i += 2) a2[i] = dbl32(a.v[i]);
-    if (RUNS) C25519_MASK_RUN_END();
+    if (RUNS) C25519_VOP2_RUN_END();
     u64 acc = 0;
 #pragma unroll
     for (int k = 0; k < 10; k++) {
@@ -151,7 +125,7 @@ C25519_DEV void fe_mul_chained(fe& r, const fe& a, const fe& b)
             y[i] = wrap ? b19[j] : b.v[j];
         }
         acc = k == 0 ? mad_chain10_from_zero(x, y) : mad_chain10(acc, x, y);
-        if (RUNS && (k % C25519_DIP_EVERY) == C25519_DIP_EVERY - 1) { C25519_MASK_RUN_BEGIN(); C25519_MASK_RUN_END(); }
+        if (RUNS) { C25519_VOP2_RUN_BEGIN(); C25519_VOP2_RUN_END(); }
         l[k] = (u32)acc & fe_mask(k);
         acc >>= fe_w(k);
     }
@@ -163,10 +137,10 @@ template <bool SCALE2, bool PLAIN = false, bool RUNS = false, typename Extra>
 C25519_DEV void fe_sqr_chained(fe& r, const fe& a, Extra extra)
 {
     u32 f2[10], f19[10], f38[10], l[10];
-    if (RUNS) C25519_MASK_RUN_BEGIN();
+    if (RUNS) C25519_VOP2_RUN_BEGIN();
 #pragma unroll
     for (int i = 0; i < 10; i++) f2[i] = dbl32(a.v[i]);
-    if (RUNS) C25519_MASK_RUN_END();
+    if (RUNS) C25519_VOP2_RUN_END();
 #pragma unroll
     for (int j = 6; j < 10; j += 2) f19[j] = a.v[j] * 19u;
 #pragma unroll
@@ -202,22 +176,20 @@ C25519_DEV void fe_sqr_chained(fe& r, const fe& a, Extra extra)
             acc = from_zero ? mad_chain6_from_zero(x, y) : mad_chain6(acc, x, y);
         }
         if (SCALE2) acc = 2 * acc + carry + extra(k);
-        if (RUNS && (k % C25519_DIP_EVERY) == C25519_DIP_EVERY - 1) { C25519_MASK_RUN_BEGIN(); C25519_MASK_RUN_END(); }
+        if (RUNS) { C25519_VOP2_RUN_BEGIN(); C25519_VOP2_RUN_END(); }
         l[k] = (u32)acc & fe_mask(k);
         carry = acc >> fe_w(k);
     }
     fe_finish_chain(r, l, carry);
 }
 
-#ifndef C25519_ALL_PRODUCT_RUNS
-#define C25519_ALL_PRODUCT_RUNS 0        // A/B knob: the in-product runs in EVERY kernel's products, not the ladder's only
-#endif
 // r = a * b.   beta_a <= 5, beta_b <= 3.3; r may alias a or b.   (ecp_MulReduce)
 C25519_DEV void fe_mul(fe& r, const fe& a, const fe& b)
 {
-    fe_mul_chained<C25519_ALL_PRODUCT_RUNS != 0>(r, a, b);
+    fe_mul_chained<false>(r, a, b);
 }
-// ... with the low-priority runs inside (the ladder's products)
+// ... with the low-priority runs inside: the ladder's products only (in every kernel's products they lost:
+// profiles/r04_ab_prio.txt, profiles/r04_ab_verify_walk.txt)
 C25519_DEV void fe_mul_runs(fe& r, const fe& a, const fe& b)
 {
     fe_mul_chained<true>(r, a, b);
@@ -230,21 +202,21 @@ C25519_DEV void fe_sqr_runs(fe& r, const fe& a)
 // r = a^2.   beta_a <= 3.3; r may alias a.   (ecp_SqrReduce)
 C25519_DEV void fe_sqr(fe& r, const fe& a)
 {
-    fe_sqr_chained<false, true, C25519_ALL_PRODUCT_RUNS != 0>(r, a, [](int) -> u64 { return 0; });
+    fe_sqr_chained<false, true, false>(r, a, [](int) -> u64 { return 0; });
 }
 
 // r = a^2 - m with the subtraction folded into the carry chain (result reduced).
 // beta_a <= 3.3, beta_m <= 2 (bias 4p).
 C25519_DEV void fe_sqr_sub(fe& r, const fe& a, const fe& m)
 {
-    fe_sqr_chained<false, false, C25519_ALL_PRODUCT_RUNS != 0>(r, a, [&](int k) -> u64 { return (u64)(2u * fe_2p(k) - m.v[k]); });
+    fe_sqr_chained<false, false, false>(r, a, [&](int k) -> u64 { return (u64)(2u * fe_2p(k) - m.v[k]); });
 }
 
 // r = 2*a^2 + p - m, folded into the carry chain (result reduced).
 // beta_a <= 2.3 (columns are doubled), p any beta < 8, m reduced (bias 2p).
 C25519_DEV void fe_sqr2_add_sub(fe& r, const fe& a, const fe& p, const fe& m)
 {
-    fe_sqr_chained<true, false, C25519_ALL_PRODUCT_RUNS != 0>(r, a, [&](int k) -> u64 { return (u64)(p.v[k] + fe_2p(k) - m.v[k]); });
+    fe_sqr_chained<true, false, false>(r, a, [&](int k) -> u64 { return (u64)(p.v[k] + fe_2p(k) - m.v[k]); });
 }
 
 C25519_DEV void fe_sqr_n(fe& r, const fe& a, int n)
@@ -437,31 +409,21 @@ C25519_DEV void fe_invert_safegcd(fe& r, const fe& z)
     fe_from_words(r, o);
 }
 
-// r = 1 / z, 0 for z = 0.  Build knob C25519_INVERT_SAFEGCD = 0: the reference's exponentiation everywhere (A/B).
-#ifndef C25519_INVERT_SAFEGCD
-#define C25519_INVERT_SAFEGCD 1
-#endif
+// r = 1 / z, 0 for z = 0: the division steps (they replaced the exponentiation everywhere: profiles/HISTORY.md, round 6,
+// "Inversion by division steps")
 C25519_DEV void fe_invert(fe& r, const fe& z)
 {
-#if C25519_INVERT_SAFEGCD
     fe_invert_safegcd(r, z);
-#else
-    fe_invert_fermat(r, z);
-#endif
 }
 
 // r = 1 / z where the four lanes of an aligned quad (lane & 3; all active) hold the same z: the division steps' three pairs on
 // three lanes (sg_divsteps30_quad) -- the operations that have a quad (quad25519.cuh) or a wave (coop25519.cuh) to themselves
 C25519_DEV void fe_invert_quad(fe& r, const fe& z)
 {
-#if C25519_INVERT_SAFEGCD
     u32 w[8], o[8];
     fe_to_words(w, z);
     sg_invert_words_quad(o, w);
     fe_from_words(r, o);
-#else
-    fe_invert_fermat(r, z);
-#endif
 }
 
 // r = x^((p-5)/8) = x^(2^252 - 3)

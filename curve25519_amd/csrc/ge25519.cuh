@@ -47,9 +47,10 @@ C25519_DEV void ge_double(ge_ext& p)
 }
 
 // p = p + q, q affine precomputed with reduced limbs.  7M.   (edp_AddAffinePoint)
-// NEED_T = false skips T3 = E*H: a doubling (or the final affine conversion) that follows never reads T.
-template <bool NEED_T = true>
-C25519_DEV void ge_add_pa(ge_ext& p, const ge_pa& q)
+// need_t = false skips T3 = E*H: a doubling (or the final affine conversion) that follows never reads T.  A run-time
+// (wave-uniform) need_t is ONE copy of the addition where the template below would put two into a loop (ge_base_mult's
+// last table: T only before the blinding point is added).
+C25519_DEV void ge_add_pa_rt(ge_ext& p, const ge_pa& q, bool need_t)
 {
     fe a, b, c, d, e, f, g, h;
     fe_sub(a, p.Y, p.X);                 // beta 3
@@ -64,30 +65,12 @@ C25519_DEV void ge_add_pa(ge_ext& p, const ge_pa& q)
     fe_add(g, d, c);                     // G = D+C   beta 3
     fe_mul(p.X, f, e);
     fe_mul(p.Y, g, h);
-    if (NEED_T) fe_mul(p.T, e, h);
-    fe_mul(p.Z, f, g);
-}
-
-// the same addition with T produced on a run-time (wave-uniform) request: ONE copy of the addition where the template
-// would put two into a loop (ge_base_mult's last table: T only before the blinding point is added)
-C25519_DEV void ge_add_pa_rt(ge_ext& p, const ge_pa& q, bool need_t)
-{
-    fe a, b, c, d, e, f, g, h;
-    fe_sub(a, p.Y, p.X);
-    fe_mul(a, a, q.ymx);
-    fe_add(b, p.Y, p.X);
-    fe_mul(b, b, q.ypx);
-    fe_mul(c, p.T, q.t2d);
-    fe_add(d, p.Z, p.Z);
-    fe_sub(e, b, a);
-    fe_add(h, b, a);
-    fe_sub(f, d, c);
-    fe_add(g, d, c);
-    fe_mul(p.X, f, e);
-    fe_mul(p.Y, g, h);
     if (need_t) fe_mul(p.T, e, h);
     fe_mul(p.Z, f, g);
 }
+
+template <bool NEED_T = true>
+C25519_DEV void ge_add_pa(ge_ext& p, const ge_pa& q) { ge_add_pa_rt(p, q, NEED_T); }
 
 // r = p + q, q projective precomputed with reduced limbs.  8M.   (edp_AddPoint)
 template <bool NEED_T = true>

@@ -92,15 +92,9 @@ C25519_DEV void sc_times_16c(u32 (&p)[N + 5], const u32* hi)
 // subtracts (L << 134 > 2^385, L << 9 > 2^260; "- p" as "+ ~p + 1" in a fixed number of words), then the split at bit 252 of
 // sc_mod: 40 + 25 + 4 multiply-adds and three carry chains, ~250 instructions; the reference's Horner fold of one top word at a
 // time (eco_ReduceHiWord eight times: sc_reduce_hi, still what sc_add uses) is ~650.  Any correct reduction gives the reference's
-// bytes: only canonical results are exported.
+// bytes: only canonical results are exported.  (The Horner fold lost: profiles/r06_ab_sc_reduce.txt.)
 C25519_DEV void sc_reduce512(u32 (&y)[8], u32 (&t)[16])
 {
-#if defined(C25519_SC_REDUCE_HORNER) && C25519_SC_REDUCE_HORNER      // A/B knob: the reference's fold, one top word at a time
-#pragma unroll
-    for (int k = 7; k >= 1; k--) sc_reduce_hi(&t[k], t[k + 8], &t[k]);
-    sc_reduce_hi(y, t[8], &t[0]);
-    return;
-#endif
     u32 p1[13], y1[13];
     sc_times_16c<8>(p1, &t[8]);
     u64 c = 1;

@@ -15,19 +15,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#if defined(C25519_CHAIN_DIP) && C25519_CHAIN_DIP               // A/B knob: a priority dip in the middle of a ten-MAD chain
-#define C25519_MID_DIP "s_setprio 0\n\ts_setprio 1\n\t"
-#else
-#define C25519_MID_DIP ""
-#endif
-#if defined(C25519_MAD_CHAIN_PRIO) && C25519_MAD_CHAIN_PRIO     // A/B knob: only the MAD chains at high wave priority
-#define C25519_CHAIN_HI "s_setprio 1\n\t"
-#define C25519_CHAIN_LO "\n\ts_setprio 0"
-#else
-#define C25519_CHAIN_HI ""
-#define C25519_CHAIN_LO ""
-#endif
-
 namespace c25519 {
 
 typedef uint32_t u32;
@@ -43,16 +30,8 @@ typedef uint64_t u64;
 // stands alone among the other waves' MADs (tools/ubench/mad_peak, profiles/r04_mad_peak.txt).  A wave that drops its
 // priority for the run is passed over while the others issue MADs and issues its run when a second wave has reached one
 // too (or nobody else can issue): the runs pair up.  Measured on the ladder: profiles/r04_ab_prio.txt.
-#ifndef C25519_VOP2_RUN_PRIO
-#define C25519_VOP2_RUN_PRIO 1        // A/B switch: 0 = no priority changes
-#endif
-#if C25519_VOP2_RUN_PRIO
 #define C25519_VOP2_RUN_BEGIN() __builtin_amdgcn_s_setprio(0)
 #define C25519_VOP2_RUN_END() __builtin_amdgcn_s_setprio(1)
-#else
-#define C25519_VOP2_RUN_BEGIN() do { } while (0)
-#define C25519_VOP2_RUN_END() do { } while (0)
-#endif
 
 // Where the compiler emits v_mad_u64_u32 for a plain C expression (a 32x32+64 multiply-add outside the asm chains): a
 // no-op here; the CPU model of these primitives counts n instructions (tests/host_emul/valu_model.h, tools/executed_macs.py),
@@ -73,19 +52,10 @@ C25519_DEV float fast_div(float a, float b) { return __fdividef(a, b); }
 
 // Three-input bitwise functions in ONE instruction (v_bitop3_b32, the truth table as an immediate: bit (4a + 2b + c) of it is the
 // result for input bits a, b, c): SHA-512's three-way XORs, Ch and Maj -- 24 XORs and 6 ANDs of a round become 12 instructions
-// (the compiler does not form them from the two-input source).  Build knob C25519_SHA_BITOP3 = 0: the two-input forms (A/B).
-#ifndef C25519_SHA_BITOP3
-#define C25519_SHA_BITOP3 1
-#endif
-#if C25519_SHA_BITOP3
+// (the compiler does not form them from the two-input source, which lost: profiles/r06_ab_sha_bitop3.txt).
 C25519_DEV u32 xor3_32(u32 a, u32 b, u32 c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
 C25519_DEV u32 ch_32(u32 e, u32 f, u32 g) { return __builtin_amdgcn_bitop3_b32(e, f, g, 0xca); }       // e ? f : g
 C25519_DEV u32 maj_32(u32 a, u32 b, u32 c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xe8); }
-#else
-C25519_DEV u32 xor3_32(u32 a, u32 b, u32 c) { return a ^ b ^ c; }
-C25519_DEV u32 ch_32(u32 e, u32 f, u32 g) { return (e & f) ^ (~e & g); }
-C25519_DEV u32 maj_32(u32 a, u32 b, u32 c) { return (a & b) ^ (a & c) ^ (b & c); }
-#endif
 
 // (hi:lo) as one 64-bit value the optimiser cannot take apart again (no instruction: the asm is empty)
 C25519_DEV u64 pair64(u32 lo, u32 hi)
@@ -204,16 +174,17 @@ C25519_DEV u32 row_carry(u64 S, u32 w, u32 mask, u32 mask_next, u32 m1, u32 m2)
 
 // acc += sum x[t]*y[t]: one asm statement per column, so the compiler cannot reassociate the chain (it would move
 // the carry-in to the end and re-create a separate 64-bit add) and does not pad every MAD with a wait state (it pads
-// asm boundaries only).  The SGPR pair receives the (never set) carry-out.
+// asm boundaries only).  The SGPR pair receives the (never set) carry-out.  (The chains alone at high wave priority, and a
+// priority dip in the middle of a ten-MAD chain, lost: profiles/r04_ab_prio.txt blocks 3 and 4.)
 C25519_DEV u64 mad_chain5(u64 acc, const u32 (&x)[5], const u32 (&y)[5])
 {
     u64 carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %7, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %7, %0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %8, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %9, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %10, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %6, %11, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %6, %11, %0"
         : "+v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]));
@@ -226,11 +197,11 @@ C25519_DEV u64 mad_chain5_from_zero(const u32 (&x)[5], const u32 (&y)[5])
 {
     u64 acc, carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %7, 0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %7, 0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %8, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %9, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %10, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %6, %11, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %6, %11, %0"
         : "=&v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]));
@@ -241,12 +212,12 @@ C25519_DEV u64 mad_chain6_from_zero(const u32 (&x)[6], const u32 (&y)[6])
 {
     u64 acc, carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %8, 0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %8, 0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %9, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %10, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %11, %0\n\t"
         "v_mad_u64_u32 %0, %1, %6, %12, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %7, %13, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %7, %13, %0"
         : "=&v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]));
@@ -257,16 +228,16 @@ C25519_DEV u64 mad_chain10_from_zero(const u32 (&x)[10], const u32 (&y)[10])
 {
     u64 acc, carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %12, 0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %12, 0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %13, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %14, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %15, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %6, %16, %0\n\t" C25519_MID_DIP
+        "v_mad_u64_u32 %0, %1, %6, %16, %0\n\t"
         "v_mad_u64_u32 %0, %1, %7, %17, %0\n\t"
         "v_mad_u64_u32 %0, %1, %8, %18, %0\n\t"
         "v_mad_u64_u32 %0, %1, %9, %19, %0\n\t"
         "v_mad_u64_u32 %0, %1, %10, %20, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %11, %21, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %11, %21, %0"
         : "=&v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]), "v"(x[8]), "v"(x[9]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]), "v"(y[6]), "v"(y[7]), "v"(y[8]), "v"(y[9]));
@@ -277,12 +248,12 @@ C25519_DEV u64 mad_chain6(u64 acc, const u32 (&x)[6], const u32 (&y)[6])
 {
     u64 carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %8, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %8, %0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %9, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %10, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %11, %0\n\t"
         "v_mad_u64_u32 %0, %1, %6, %12, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %7, %13, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %7, %13, %0"
         : "+v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]));
@@ -293,16 +264,16 @@ C25519_DEV u64 mad_chain10(u64 acc, const u32 (&x)[10], const u32 (&y)[10])
 {
     u64 carry_out;
     asm(
-        C25519_CHAIN_HI "v_mad_u64_u32 %0, %1, %2, %12, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %2, %12, %0\n\t"
         "v_mad_u64_u32 %0, %1, %3, %13, %0\n\t"
         "v_mad_u64_u32 %0, %1, %4, %14, %0\n\t"
         "v_mad_u64_u32 %0, %1, %5, %15, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %6, %16, %0\n\t" C25519_MID_DIP
+        "v_mad_u64_u32 %0, %1, %6, %16, %0\n\t"
         "v_mad_u64_u32 %0, %1, %7, %17, %0\n\t"
         "v_mad_u64_u32 %0, %1, %8, %18, %0\n\t"
         "v_mad_u64_u32 %0, %1, %9, %19, %0\n\t"
         "v_mad_u64_u32 %0, %1, %10, %20, %0\n\t"
-        "v_mad_u64_u32 %0, %1, %11, %21, %0" C25519_CHAIN_LO
+        "v_mad_u64_u32 %0, %1, %11, %21, %0"
         : "+v"(acc), "=s"(carry_out)
         : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]), "v"(x[8]), "v"(x[9]),
           "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]), "v"(y[4]), "v"(y[5]), "v"(y[6]), "v"(y[7]), "v"(y[8]), "v"(y[9]));

@@ -41,9 +41,6 @@ constexpr int LAT_CAP_BITS = 158;          // what the 40-digit signed walk can 
 #endif
 constexpr int LAT_LEHMER_STOP = 128;        // Lehmer steps bring the smaller remainder down to this many bits; the
                                             // exact steps (ten times dearer per bit) only finish: 128 / 129 bits
-#ifndef C25519_LAT_BALANCED_STOP
-#define C25519_LAT_BALANCED_STOP 1          // A/B switch: 0 = round 2's stopping rule (both remainders down to 128 / 129 bits)
-#endif
 constexpr int LAT_R = 8, LAT_T = 6;        // words of a remainder (unsigned) / of a cofactor (two's complement)
 
 template <int W>
@@ -154,9 +151,6 @@ C25519_DEV void lat_modulus(u32 (&n)[8])
     for (int i = 1; i < 8; i++) n[i] = (K_L[i] << 3) | (K_L[i - 1] >> 29);
 }
 
-#ifndef C25519_LAT_QUOTIENT_STEPS
-#define C25519_LAT_QUOTIENT_STEPS 1        // A/B switch: 0 = the shift-subtract inner loop of round 2
-#endif
 // an estimate of xa / xb (xb != 0) that never exceeds the true quotient, and is at least 1 when xa >= xb: the top 32 bits of
 // xa against the same bits of xb plus one, divided in single precision and scaled down by more than the rounding errors add up to
 C25519_DEV u32 lat_quot_est(u64 xa, u64 xb)
@@ -178,10 +172,9 @@ C25519_DEV bool lat_lehmer_step(u32 (&r0)[LAT_R], u32 (&t0)[LAT_T], u32 (&r1)[LA
     u64 x0 = leading62<LAT_R>(r0, top, words), x1 = leading62<LAT_R>(r1, top, words);
     // x0 = A*a - B*b, x1 = -C*a + D*b for the original leading parts (a, b); entries only ever grow
     u32 A = 1, B = 0, C = 0, D = 1;
-#if C25519_LAT_QUOTIENT_STEPS
     // Euclid on the leading parts with estimated quotients, the two remainders taking turns: x0 -= q x1, then x1 -= q x0.  No
-    // role selects (the shift-subtract form below spends most of its 72 instructions per trip on them), and a step removes
-    // 1.7 bits on average instead of 1.3.  q comes from a float division of the top 32 bits, scaled so that it can only
+    // role selects (round 2's shift-subtract form spent most of its 72 instructions per trip on them), and a step removes
+    // 1.7 bits on average instead of 1.3 (profiles/r03_ab_verify_structure.txt block 10).  q comes from a float division of the top 32 bits, scaled so that it can only
     // UNDER-estimate (lat_quot_est); any q keeps the transformation unimodular, a small one just makes less progress.
     auto half_step = [&](u64& xa, const u64 xb, u32& Ma0, u32& Ma1, const u32 Mb0, const u32 Mb1) -> bool {
         u32 q = lat_quot_est(xa, xb);
@@ -204,30 +197,6 @@ C25519_DEV bool lat_lehmer_step(u32 (&r0)[LAT_R], u32 (&t0)[LAT_T], u32 (&r1)[LA
         if (!__any(g0 || g1)) break;
         C25519_LAT_COUNT(lehmer_inner);
     }
-#else
-#pragma unroll 1
-    for (int it = 0; it < 48; it++) {
-        const bool c = x0 >= x1;
-        const u64 big = c ? x0 : x1, small = c ? x1 : x0;
-        const u32 ms0 = c ? C : A, ms1 = c ? D : B, mb0 = c ? A : C, mb1 = c ? B : D;     // rows of small / big
-        int k = bitlen64(big) - bitlen64(small);
-        u64 sh = small << k;
-        if (sh > big) { k -= 1; sh >>= 1; }
-        const u64 n0 = (u64)mb0 + ((u64)ms0 << k), n1 = (u64)mb1 + ((u64)ms1 << k);
-        // keep the matrix below 2^31 and the smaller leading part above 2^33 (below that its low bits are noise); stop
-        // where the exact steps take over (the smaller remainder down to LAT_LEHMER_STOP bits)
-        const bool go = active && small >= ((u64)1 << 33) && k < 31 && n0 < ((u64)1 << 31) && n1 < ((u64)1 << 31)
-                        && bitlen64(small) + scale > LAT_LEHMER_STOP;
-        if (!__any(go)) break;
-        C25519_LAT_COUNT(lehmer_inner);
-        if (go) {
-            const u64 nb = big - sh;
-            x0 = c ? nb : x0; x1 = c ? x1 : nb;
-            A = c ? (u32)n0 : A; B = c ? (u32)n1 : B;
-            C = c ? C : (u32)n0; D = c ? D : (u32)n1;
-        }
-    }
-#endif
     const bool progressed = active && !(A == 1 && B == 0 && C == 0 && D == 1);
     // apply exactly: (r0, r1) <- (A r0 - B r1, -C r0 + D r1), same for the cofactors (two's complement, sign-extended)
     u32 x[LAT_R + 1], y[LAT_R + 1], n0[LAT_R + 1], n1[LAT_R + 1];
@@ -294,13 +263,13 @@ C25519_DEV u32 sc_lattice_short(u32 (&rho)[5], u32 (&tau)[5], u32& tau_negative,
         for (int i = 0; i < LAT_T; i++) mag[i] = (c ? t1[i] : t0[i]) ^ (0u - ((c ? t1[LAT_T - 1] : t0[LAT_T - 1]) >> 31));
         const int lt_small = bitlen_words<LAT_T>(mag);
         const bool room = lt_small + k0 <= 32 * LAT_T - 3;
-#if C25519_LAT_BALANCED_STOP
         // The first vector whose remainder is below 2^128 has a cofactor below N / 2^128 = 2^127.5 (|T_(i+1)| r_i < N):
         // when that cofactor is odd it is the answer and nothing is left to do.  When it is even, the other vector (odd
         // cofactor) is the answer, and a step on it -- remainder one bit shorter, cofactor up to |T_small| << k -- is wanted
         // only while it shortens the longer of the two: the remainder is the longer one and the new cofactor stays below it.
         // (Round 2's rule ran both remainders down to 128 / 129 bits whatever that did to the cofactor: vectors of up to
-        // 139 bits, every second wave starting its walk a digit higher, and four exact steps per wave instead of two.)
+        // 139 bits, every second wave starting its walk a digit higher, and four exact steps per wave instead of two:
+        // profiles/r03_ab_verify_structure.txt block 12.)
         u32 magb[LAT_T];
 #pragma unroll
         for (int i = 0; i < LAT_T; i++) magb[i] = (c ? t0[i] : t1[i]) ^ (0u - ((c ? t0[LAT_T - 1] : t1[LAT_T - 1]) >> 31));
@@ -308,9 +277,6 @@ C25519_DEV u32 sc_lattice_short(u32 (&rho)[5], u32 (&tau)[5], u32& tau_negative,
         const bool small_even = ((c ? t1[0] : t0[0]) & 1u) == 0;
         const bool improve_big = small_even && lbig > lt_big && lt_small + k0 < lbig;
         const bool want = sane && !stopped && room && lsmall != 0 && (lsmall > 128 || improve_big);
-#else
-        const bool want = sane && !stopped && room && lsmall != 0 && (lsmall > 128 || lbig > 129);
-#endif
         stopped = stopped || (sane && !room);
         if (!__any(want)) break;
         C25519_LAT_COUNT(exact_steps);
@@ -459,9 +425,6 @@ C25519_DEV void sc_comb_columns(u32 (&cols)[SIGMA_WORDS], const u32 (&k)[8])
 // per field.  Packing is a plain positional sum (limb i at bit ceil(25.5 i)), so limbs need not be strictly below 2^w, only
 // the value below 2^256 (true of a product's output and of fe_carry32's); unpacking is fe_from_words, bit 255 included.
 constexpr int ROW_WORDS = 32;
-#ifndef C25519_WALK_PREFETCH
-#define C25519_WALK_PREFETCH 1       // A/B switch: 0 = the walk loads each row field right before the product that uses it
-#endif
 
 C25519_DEV void fe_pack_words(u32 (&w)[8], const fe& a)
 {
@@ -574,7 +537,7 @@ C25519_DEV void ge_add_pe_row(ge_ext& S, const u32* row, u32 neg)
 // digit round at the TOP of the round -- their addresses only depend on the round's digits -- so the loads are 12 000
 // cycles old when the additions want them: measured 4.5 % of the pass against loading each field right before its product
 // (profiles/r03_ab_verify_structure.txt block 8), at two waves per SIMD instead of three (64 more registers), which the
-// VALU-bound walk does not mind.  -row: the words of Y+X and Y-X trade places before they are unpacked.
+// VALU-bound walk does not mind (again in profiles/r04_ab_verify_walk.txt).  -row: the words of Y+X and Y-X trade places before they are unpacked.
 struct packed_row { uint4 q[8]; };
 C25519_DEV void row_fetch(packed_row& r, const u32* row)
 {
@@ -833,12 +796,10 @@ C25519_DEV u32 ge_walk_is_neutral(const WalkScalars& sc, const u32* tq, const u3
 #pragma unroll 1
     for (int i = top - 1; i >= 0; i--) {
         const u32 tw = sc.tau_word(i >> 3), rw = sc.rho_word(i >> 3);      // in flight under the doublings
-#if C25519_WALK_PREFETCH
         u32 negq, negr;
         packed_row rq, rr;
         row_fetch(rq, tq + signed16_of(negq, tw, i & 7) * ROW_WORDS);
         row_fetch(rr, tr + signed16_of(negr, rw, i & 7) * ROW_WORDS);
-#endif
         if (i >= SC_ROUNDS) {
 #pragma unroll 1
             for (int j = 0; j < 3; j++) ge_double<false>(S);
@@ -853,16 +814,8 @@ C25519_DEV u32 ge_walk_is_neutral(const WalkScalars& sc, const u32* tq, const u3
                 cols >>= 16;
             }
         }
-#if C25519_WALK_PREFETCH
         ge_add_pe_regs<true>(S, rq, negq);
         ge_add_pe_regs<false>(S, rr, negr);
-#else
-        u32 neg;
-        const u32 mq = signed16_of(neg, tw, i & 7);
-        ge_add_pe_row<true>(S, tq + mq * ROW_WORDS, neg);
-        const u32 mr = signed16_of(neg, rw, i & 7);
-        ge_add_pe_row<false>(S, tr + mr * ROW_WORDS, neg);
-#endif
     }
     // neutral element: X == 0 and Y == Z (Z != 0 for on-curve inputs under the complete law)
     u32 xw[8], dw[8], acc = 0;

@@ -34,45 +34,31 @@ C25519_DEV void mont_double(fe& X, fe& Z)
     fe_mul_runs(Z, B, A);
 }
 
-#ifndef C25519_LADDER_PRIO_SITES
-#define C25519_LADDER_PRIO_SITES 0
-#endif
-
 // no-op section marker of the product build; the opt-in cycle-probe build (engine.hip, -DC25519_CYCLE_PROBE=2) passes
 // one that reads s_memtime, so that the sections of a step can be timed in place (tools/cycle_probe.py)
 struct NoSectionMark { C25519_DEV void operator()(int) const {} };
 
 // BASE9: the difference point is the curve's base point u = 9 (curve25519_dh_CalculatePublicKey), so the
 // one multiplication by it is a 10-MAD small-constant multiply instead of a full product.
+// (the step's add / sub runs get their low priority from the field layer's brackets, which replaced brackets placed here:
+// profiles/r04_ab_prio.txt blocks 2 and 4)
 template <bool BASE9 = false, typename Mark = NoSectionMark>
 C25519_DEV void ladder_step(fe& SX, fe& SZ, fe& DX, fe& DZ, const fe& base, u32 prev_eq, Mark mark = Mark())
 {
     fe A, B, C, Dp, P, M;
-#if C25519_LADDER_PRIO_SITES >= 1
-    C25519_VOP2_RUN_BEGIN();
-#endif
     fe_sub(A, SX, SZ);                 // beta 3
     fe_add(B, SX, SZ);                 // beta 2
     fe_sub(C, DX, DZ);                 // beta 3
     fe_add(Dp, DX, DZ);                // beta 2
     fe_select(P, prev_eq, Dp, B);      // doubling input, x+z
     fe_select(M, prev_eq, C, A);       // doubling input, x-z
-#if C25519_LADDER_PRIO_SITES >= 1
-    C25519_VOP2_RUN_END();
-#endif
     mark(0);
     fe_mul_runs(A, A, Dp);                  // (x1-z1)(x2+z2)
     mark(1);
     fe_mul_runs(B, C, B);                   // (x2-z2)(x1+z1)
     mark(2);
-#if C25519_LADDER_PRIO_SITES >= 2
-    C25519_VOP2_RUN_BEGIN();
-#endif
     fe_add(C, A, B);                   // beta 2
     fe_sub(B, A, B);                   // beta 3
-#if C25519_LADDER_PRIO_SITES >= 2
-    C25519_VOP2_RUN_END();
-#endif
     mark(3);
     fe_sqr_runs(SX, C);                     // x3
     fe_sqr_runs(A, B);
@@ -85,13 +71,7 @@ C25519_DEV void ladder_step(fe& SX, fe& SZ, fe& DX, fe& DZ, const fe& base, u32 
     mark(6);
     fe_mul_runs(DX, A, B);                  // x4
     mark(7);
-#if C25519_LADDER_PRIO_SITES >= 3
-    C25519_VOP2_RUN_BEGIN();
-#endif
     fe_sub(B, A, B);                   // beta 3
-#if C25519_LADDER_PRIO_SITES >= 3
-    C25519_VOP2_RUN_END();
-#endif
     fe_mul121665_add(A, A, B);         // (x+z)^2 + 121665*B
     mark(8);
     fe_mul_runs(DZ, B, A);                  // z4
