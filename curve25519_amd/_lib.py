@@ -44,6 +44,10 @@ SIGNATURES = {
     "ed25519_VerifySignature_strict_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_VerifySignature_strict_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_strict_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_VerifySignature_zip215_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VerifySignature_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VerifySignature_zip215_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_VerifySignature_zip215_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],

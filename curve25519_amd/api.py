@@ -219,6 +219,35 @@ def ed25519_VerifySignature(sig, pk, msg, strict=False):
     return ok
 
 
+def ed25519_VerifySignature_zip215(sig, pk, msg):
+    """n x ZIP-215 verification (include/curve25519_amd.h: S < L, key and R in any encoding that decodes, the cofactored equation
+    [8]([S]B - [k]A - R) = O).  Returns int32[n] of 1 (valid) / 0 (invalid)."""
+    sig = _np(sig, 64, "sig")
+    pk = _np(pk, 32, "pk")
+    n = sig.shape[0]
+    if pk.shape[0] != n:
+        raise ValueError("sig and pk must have the same number of rows")
+    msg, msg_size = _msgs(msg, n)
+    ok = np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_VerifySignature_zip215_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n),
+               "ed25519_VerifySignature_zip215_batch")
+    return ok
+
+
+def ed25519_VerifySignature_zip215_ragged(sig, pk, messages):
+    """ed25519_VerifySignature_zip215 with per-element message lengths (`messages`: sequence of bytes-like)."""
+    sig = _np(sig, 64, "sig")
+    pk = _np(pk, 32, "pk")
+    n = sig.shape[0]
+    if len(messages) != n or pk.shape[0] != n:
+        raise ValueError("one message and one key per signature")
+    flat, offsets = _ragged(messages)
+    ok = np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_VerifySignature_zip215_ragged_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(flat), _ptr(offsets), n),
+               "ed25519_VerifySignature_zip215_ragged_batch")
+    return ok
+
+
 def ed25519_Verify_Init(pk):
     """n x ed25519_Verify_Init: per-key contexts, uint8[n, 2080] (pk || 16 rows x 4 canonical elements)."""
     pk = _np(pk, 32, "pk")
@@ -433,6 +462,16 @@ def ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=False):
 def ed25519_VerifySignature_strict_dev(verdict, sig, pk, msg):
     """Device form of ed25519_VerifySignature_strict: verdict int32[n, 1]."""
     ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=True)
+
+
+def ed25519_VerifySignature_zip215_dev(verdict, sig, pk, msg):
+    """Device form of ed25519_VerifySignature_zip215: verdict int32[n, 1]."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
+            _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_VerifySignature_zip215_dev(*args, msg.shape[1], n, st), "ed25519_VerifySignature_zip215_dev")
 
 
 def ed25519_Verify_Check_strict_dev(verdict, ctx, sig, msg):

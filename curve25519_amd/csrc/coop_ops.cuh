@@ -37,6 +37,10 @@ C25519_DEV u32 strict_key_flags(u32 f, u32 ok)
 {
     return (!ok || (f & FLAG_REJECT)) ? FLAG_REJECT | FLAG_SLOW : (f & FLAG_FITS) ? FLAG_KEY_OK : FLAG_KEY_OK | FLAG_SLOW;
 }
+// the ZIP-215 lattice path: rule 1 (S < L) in the scalar step, as FLAG_REJECT; the key lane of the point step then decides exactly as
+// the strict one does (strict_key_flags with ok = "the key has a square root"): rejected elements are skipped by the walk and listed
+// nowhere, so the slow list holds over-long vectors only
+C25519_DEV u32 zip215_pair_flags(const u32 (&Sw)[8]) { return ~strict_less(Sw, K_L) & FLAG_REJECT; }
 
 namespace coop {
 
@@ -357,7 +361,9 @@ constexpr int V3_LDS_WORDS = V3_BASE2 + V3_ROWQ2 + SC_ROUNDS * 4 * 64;
 // key on the curve; R decodes canonically)
 // Strict (the strict calls): wave 0 also tests S < L and R's y, wave 2 the key's y; an element that breaks a rule gets verdict 0
 // there and never goes on the slow list.
-template <bool Strict = false>
+// Zip215 (the ZIP-215 calls): wave 0 tests S < L, waves 1 and 2 decode without the canonical-encoding term; a key or an R without a
+// square root, or S >= L, gets verdict 0 here and goes on no list; wave 0 doubles the sum three times in front of the neutral test.
+template <bool Strict = false, bool Zip215 = false>
 C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const FastScratch& fs, int* verdict, const void* sig, const void* pk,
                                    const Msgs& msgs, size_t n, size_t e, const u32* __restrict__ g_tbl)
 {
@@ -378,6 +384,7 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
             hand[0] = tau_neg;
             hand[1] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8);
             if (Strict) hand[1] |= strict_pair_flags(Rw, Sw);
+            if (Zip215) hand[1] |= zip215_pair_flags(Sw);
         }
     } else {
         // ed_verify_fast_decode (verify_fast.cuh) by a whole wave each: wave 1 takes R -- which must be the canonical encoding of a
@@ -404,7 +411,7 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
         for (int i = 0; i < 8; i++) diff |= cw[i] ^ yw[i];
         // y < p, and the sign bit an encoder would have produced: x = 0 has parity 0 only
         const u32 canonical = (diff == 0 && !(x_zero && (parity & 1u))) ? 0xffffffffu : 0u;
-        ok &= ~is_r | canonical;
+        if (!Zip215) ok &= ~is_r | canonical;
         if (Strict) ok &= is_r | ~strict_reject_key(w);
         const u32 neg = carry_small(L, (u64)(L.p2 - xl));
         if (is_r) xl = neg;
@@ -416,7 +423,8 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
     }
     __syncthreads();
     const u32 f = hand[1] | (hand[2] ? FLAG_KEY_OK : 0u) | (hand[3] ? FLAG_R_OK : 0u);
-    if (Strict && ((f & FLAG_REJECT) || !(f & FLAG_KEY_OK))) {             // rules 1-5 (a key off the curve breaks rule 4)
+    if ((Strict && ((f & FLAG_REJECT) || !(f & FLAG_KEY_OK)))              // rules 1-5 (a key off the curve breaks rule 4)
+        || (Zip215 && ((f & FLAG_REJECT) || (f & (FLAG_KEY_OK | FLAG_R_OK)) != (FLAG_KEY_OK | FLAG_R_OK)))) {   // ZIP-215 rules 1-3
         if (threadIdx.x == 0) {
             fs.flags[e] = f | FLAG_REJECT;
             verdict[e] = 0;
@@ -454,6 +462,10 @@ C25519_DEV void verify_three_waves(u32* lds_all, u32* park, u32* hand, const Fas
     if (wave != 0) return;
     v = ge_add_pe(lds, L, v, V3_HANDOVER, 0u);
     v = ge_add_pe(lds, L, v, V3_HANDOVER + 4, 0u);
+    if (Zip215) {
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) v = ge_dbl(lds, L, v);
+    }
     const u32 neutral = is_neutral(lds, L, v);
     if (lane == 0) verdict[e] = (neutral & f & FLAG_R_OK) ? 1 : 0;
 }

@@ -450,29 +450,36 @@ int ed25519_SignMessage_blinded_batch(unsigned char* sig, const unsigned char* p
     return sign_batch(sig, priv, blinding, msg, msg_size, n);
 }
 
+// rules: 0 the plain call, 1 strict, 2 ZIP-215
 static int verify_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msg, size_t msg_size,
-                        size_t n, bool strict)
+                        size_t n, int rules)
 {
+    const auto dev = rules == 2 ? ed25519_VerifySignature_zip215_dev : rules == 1 ? ed25519_VerifySignature_strict_dev : ed25519_VerifySignature_dev;
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ pk, nullptr, 32 }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return (strict ? ed25519_VerifySignature_strict_dev : ed25519_VerifySignature_dev)(d[3], d[0], d[1], d[2],
-                                                                                                            msg_size, c, st);
+                         return dev(d[3], d[0], d[1], d[2], msg_size, c, st);
                      });
 }
 
 int ed25519_VerifySignature_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                   const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, false);
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, 0);
 }
 
 int ed25519_VerifySignature_strict_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, true);
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, 1);
+}
+
+int ed25519_VerifySignature_zip215_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                         const unsigned char* msg, size_t msg_size, size_t n)
+{
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, 2);
 }
 
 // ragged messages: message i is msgs[offsets[i] .. offsets[i+1]); offsets has n+1 entries (host memory).
@@ -512,8 +519,10 @@ int ed25519_SignMessage_ragged_batch(unsigned char* sig, const unsigned char* pr
 }
 
 static int verify_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msgs,
-                               const uint64_t* offsets, size_t n, bool strict)
+                               const uint64_t* offsets, size_t n, int rules)
 {
+    const auto dev = rules == 2 ? ed25519_VerifySignature_zip215_ragged_dev
+                     : rules == 1 ? ed25519_VerifySignature_strict_ragged_dev : ed25519_VerifySignature_ragged_dev;
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
@@ -528,8 +537,7 @@ static int verify_ragged_batch(int* verdict, const unsigned char* sig, const uns
     C25519_RC(t.reserve_dev(L, 2, sizeof(int) * n));
     C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], sig, 64 * n, hipMemcpyHostToDevice, st));
     C25519_TRY(hipMemcpyAsync(t.dbuf[L][1], pk, 32 * n, hipMemcpyHostToDevice, st));
-    C25519_RC((strict ? ed25519_VerifySignature_strict_ragged_dev : ed25519_VerifySignature_ragged_dev)(
-        t.dbuf[L][2], t.dbuf[L][0], t.dbuf[L][1], d_msgs, (const uint64_t*)d_off, n, st));
+    C25519_RC(dev(t.dbuf[L][2], t.dbuf[L][0], t.dbuf[L][1], d_msgs, (const uint64_t*)d_off, n, st));
     C25519_TRY(hipMemcpyAsync(verdict, t.dbuf[L][2], sizeof(int) * n, hipMemcpyDeviceToHost, st));
     C25519_TRY(hipStreamSynchronize(st));
     return 0;
@@ -538,13 +546,19 @@ static int verify_ragged_batch(int* verdict, const unsigned char* sig, const uns
 int ed25519_VerifySignature_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msgs, const uint64_t* offsets, size_t n)
 {
-    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, false);
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 0);
 }
 
 int ed25519_VerifySignature_strict_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                                 const unsigned char* msgs, const uint64_t* offsets, size_t n)
 {
-    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, true);
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 1);
+}
+
+int ed25519_VerifySignature_zip215_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
+                                                const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 2);
 }
 
 // ---- the reference's single-call API: a device batch of one, fatal on device failure --------------

@@ -659,6 +659,160 @@ __global__ void __launch_bounds__(SM_BLOCK) k_ed25519_verify_check_strict_mask(i
     }
 }
 
+// ---- ed25519_VerifySignature_zip215_*: the lattice path under the ZIP-215 rule ---------------------------------------------------------
+// Twins of the lattice path's kernels, written out and kept behind them (as templates of the plain kernels, or in between them, they
+// changed the plain kernels' gfx950 code, which must stay what it was).  The walk computes W = [rho](S*B - k*A - R) with rho odd:
+// multiplication by rho permutes the 8-torsion, so [8]W = O is the rule's equation.  The quad and per-wave walks double W three times
+// in front of the neutral test.  The lane path has no walk of its own -- any twin of k_ed25519_verify_fast_walk changed that kernel's
+// code -- and hands the plain walk scalars multiplied by 8 instead (ed_verify_zip215_scalars), at 0.75 digit rounds per wave.
+// S >= L (FLAG_REJECT from the scalar step) and a key without a square root get verdict 0 where the key is decoded and go on no list;
+// an R without one gets 0 from the walk or the fallback.  The slow list holds over-long vectors only, and its kernel is cofactored too.
+template <bool Scale8>
+C25519_DEV void verify_scalars_lane_zip215(const FastScratch& fs, const void* sig, const void* pk, const Msgs& msgs, size_t n, size_t i)
+{
+    u32 pkw[8], Rw[8], Sw[8], cols[SIGMA_WORDS], rho[5], tau[5], tau_neg;
+    load32(pkw, pk, i);
+    load32(Rw, sig, 2 * i);
+    load32(Sw, sig, 2 * i + 1);
+    const u32 lat_ok = ed_verify_zip215_scalars(cols, rho, tau, tau_neg, pkw, Rw, Sw, msgs.ptr(i), msgs.len(i), fs.lat_cap_bits, Scale8);
+#pragma unroll
+    for (int w = 0; w < SIGMA_WORDS; w++) fs.sigma[(size_t)w * n + i] = cols[w];
+#pragma unroll
+    for (int w = 0; w < 5; w++) { fs.rho[(size_t)w * n + i] = rho[w]; fs.tau[(size_t)w * n + i] = tau[w]; }
+    const int top = lat_ok ? walk_top_digit(tau, rho) : 0;
+    load32(Sw, sig, 2 * i + 1);                              // S again from L2, as the strict lane does
+    fs.flags[i] = (lat_ok & FLAG_FITS) | (tau_neg & FLAG_TAU_NEG) | ((u32)top << 8) | zip215_pair_flags(Sw);
+}
+
+__global__ void __launch_bounds__(FS_BLOCK) k_ed25519_verify_fast_scalars_zip215(FastScratch fs, const void* sig, const void* pk,
+                                                                                 Msgs msgs, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * FS_BLOCK + threadIdx.x;
+    if (i == 0) fs.slow_count[0] = fs.slow_count[1] = fs.slow_count[2] = 0;
+    if (i >= n) return;
+    verify_scalars_lane_zip215<true>(fs, sig, pk, msgs, n, i);   // scalars times 8: the plain walk kernel then tests [8]W
+}
+
+// k_ed25519_verify_fast_points under the ZIP-215 rule: both points by ed_zip215_decode (no canonical-encoding term).  A key without a square root, or an
+// element with S >= L, gets verdict 0 here and is marked as listed without being listed; an R without one leaves FLAG_R_OK clear
+// (the walk, or the fallback for an over-long vector, then answers 0).
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_fast_points_zip215(FastScratch fs, const void* sig,
+                                                                                                 const void* pk, size_t n, int* verdict)
+{
+    const size_t j = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (j >= 2 * n) return;
+    const bool is_r = j >= n;
+    const size_t e = is_r ? j - n : j;
+    u32 w[8];
+    if (is_r) load32(w, sig, 2 * e); else load32(w, pk, e);
+    const u32 f = fs.flags[e];
+    fe X, Y;
+    const u32 ok = ed_zip215_decode(X, Y, w, (is_r || !(f & FLAG_TAU_NEG)) ? 0xffffffffu : 0u);
+    if (!is_r) {                                                   // the walk's order (see FastScratch::order)
+        const bool is_long = ((f >> 8) & 63u) > 33u;               // (scalars times 8: a digit later than the plain kernel's split)
+        const u32 pos = is_long ? (u32)n - 1u - atomicAdd(fs.slow_count + 2, 1u) : atomicAdd(fs.slow_count + 1, 1u);
+        fs.order[pos] = (u32)e;
+    }
+    if (is_r) {
+        if (ok) atomicOr(&fs.flags[e], FLAG_R_OK);
+    } else {
+        const u32 add = strict_key_flags(f, ok);
+        atomicOr(&fs.flags[e], add);
+        if (add & FLAG_REJECT) verdict[e] = 0;
+        else if (add & FLAG_SLOW) fs.slow_list[atomicAdd(fs.slow_count, 1u)] = (u32)e;
+    }
+    wtable_build(fs.tables + e * FAST_TABLE_WORDS + (is_r ? WTABLE_WORDS : 0), X, Y);
+}
+
+// k_ed25519_verify_quad_prep: rule 1 in the scalar lanes, both points by ed_zip215_decode as decoded (the walk flips the key's rows)
+__global__ void __launch_bounds__(ED_BLOCK, C25519_VD_WAVES) k_ed25519_verify_quad_prep_zip215(FastScratch fs, const void* sig, const void* pk,
+                                                                                                Msgs msgs, size_t n, unsigned scalar_blocks)
+{
+    if (blockIdx.x < scalar_blocks) {
+        const size_t i = (size_t)blockIdx.x * FS_BLOCK + threadIdx.x;
+        if (i == 0) fs.slow_count[0] = fs.slow_count[1] = fs.slow_count[2] = 0;
+        if (i >= n) return;
+        verify_scalars_lane_zip215<false>(fs, sig, pk, msgs, n, i);
+        return;
+    }
+    const size_t j = (size_t)(blockIdx.x - scalar_blocks) * ED_BLOCK + threadIdx.x;
+    if (j >= 2 * n) return;
+    const bool is_r = j >= n;
+    const size_t e = is_r ? j - n : j;
+    u32 w[8];
+    if (is_r) load32(w, sig, 2 * e); else load32(w, pk, e);
+    fe X, Y;
+    const u32 ok = ed_zip215_decode(X, Y, w, 0xffffffffu);      // -A (tau's sign is not known yet) and -R
+    fs.pflags[j] = ok;
+    wtable_build(fs.tables + e * FAST_TABLE_WORDS + (is_r ? WTABLE_WORDS : 0), X, Y);
+}
+
+// k_ed25519_verify_quad_walk: S >= L, a key or an R without a square root: verdict 0, listed nowhere; [8]W in front of the neutral test
+__global__ void __launch_bounds__(QW_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2)))
+k_ed25519_verify_quad_walk_zip215(FastScratch fs, int* verdict, size_t n, const u32* __restrict__ g_tbl)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds_tbl[SC_TBL_WORDS];
+    lds_stage_words(lds_tbl, g_tbl + SC_TBL_OFFSET, SC_TBL_WORDS);
+    const size_t i = (size_t)blockIdx.x * (QW_BLOCK / 4) + (threadIdx.x >> 2);
+    const u32 f = i < n ? fs.flags[i] : 0u;
+    const u32 key_ok = i < n ? fs.pflags[i] : 0u, r_ok = i < n ? fs.pflags[n + i] : 0u;
+    const bool rejected = i < n && ((f & FLAG_REJECT) || !key_ok || !r_ok);
+    const bool walks = !rejected && (f & FLAG_FITS);
+    int top = walks ? (int)((f >> 8) & 63u) : 0;           // the wave walks from its longest element's first digit
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int other = __shfl_xor(top, o);
+        top = other > top ? other : top;
+    }
+    top = __builtin_amdgcn_readfirstlane(top);
+    const quad::Roles R = quad::roles();
+    if (!walks) {                                         // (whole quads leave)
+        if (rejected && R.is0) verdict[i] = 0;
+        else if (i < n && R.is0) fs.slow_list[atomicAdd(fs.slow_count, 1u)] = (u32)i;
+        return;
+    }
+    const u32* tq = fs.tables + i * FAST_TABLE_WORDS;
+    const WalkScalars sc{ fs.sigma, fs.tau, fs.rho, n, i };
+    const u32 q_flip = (f & FLAG_TAU_NEG) ? 0xffffffffu : 0u;
+    const u32 neutral = quad::walk_is_neutral<true>(sc, tq, tq + WTABLE_WORDS, lds_tbl, top < 8 ? 8 : top, R, q_flip);
+    if (R.is0) verdict[i] = neutral ? 1 : 0;
+}
+
+// k_ed25519_verify_one_per_group: coop::verify_three_waves in its ZIP-215 form
+__global__ void __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 2)))
+k_ed25519_verify_one_per_group_zip215(FastScratch fs, int* verdict, const void* sig, const void* pk, Msgs msgs, size_t n,
+                                      const u32* __restrict__ g_tbl)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds_all[coop::V3_LDS_WORDS];
+    __shared__ u32 park[40], hand[4];
+    if (blockIdx.x >= n) return;
+    coop::verify_three_waves<false, true>(lds_all, park, hand, fs, verdict, sig, pk, msgs, n, blockIdx.x, g_tbl);
+}
+
+// k_ed25519_verify_slow: after a ZIP-215 call the list holds over-long vectors only (keys on the curve), and the verdict is the
+// cofactored one (ed_verify_zip215_reference_order); same protocol (slow_report, the completion word of a call of one)
+__global__ void __launch_bounds__(ED_BLOCK, 2) k_ed25519_verify_slow_zip215(FastScratch fs, int* verdict, const void* sig, const void* pk,
+                                                                            Msgs msgs, const u32* __restrict__ g_tbl, DoneWord done)
+{
+    const u32 count = *fs.slow_count;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *fs.slow_report = count;
+        if (count == 0) signal_done(done);
+    }
+    if ((size_t)blockIdx.x * ED_BLOCK >= count) return;
+    __shared__ __attribute__((aligned(16))) u32 lds_tbl[PA_WORDS * 256];
+    lds_stage_words(lds_tbl, g_tbl + REF_TBL_OFFSET, REF_TBL_WORDS);
+    const size_t k = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (k >= count) return;
+    const size_t i = fs.slow_list[k];
+    u32 pkw[8], Rw[8], Sw[8];
+    load32(pkw, pk, i);
+    load32(Rw, sig, 2 * i);
+    load32(Sw, sig, 2 * i + 1);
+    verdict[i] = ed_verify_zip215_reference_order(pkw, Rw, Sw, msgs.ptr(i), msgs.len(i), fs.tables + i * FAST_TABLE_WORDS, lds_tbl);
+    if (k == 0) signal_done(done);
+}
+
 namespace {
 
 // scratch of one verification pass: per-lane tables (the larger of the two paths' formats: they never live at the same
@@ -685,11 +839,14 @@ thread_local LastVerify tl_last_verify;
 struct LastCheck { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
 thread_local LastCheck tl_last_check;
 
-// strict (fast only): the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh)
+// rules (fast only): RULES_STRICT runs the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh), RULES_ZIP215
+// the *_zip215 ones (cofactored equation, any point encoding, S < L) with their own kernel for the slow list
+enum VerifyRules { RULES_PLAIN, RULES_STRICT, RULES_ZIP215 };
 template <typename MakeFin>
 int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin,
-               bool strict = false)
+               VerifyRules rules = RULES_PLAIN)
 {
+    const bool strict = rules == RULES_STRICT, zip215 = rules == RULES_ZIP215;
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
     void* w = nullptr;
@@ -718,30 +875,34 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
         }
         if (!verify_quad_for(n) && verify_coop_for(n)) {   // a few elements: one launch, three waves per element
             C25519_TRY(hipMemsetAsync(fs.slow_count, 0, 3 * sizeof(u32), stream));
-            (strict ? k_ed25519_verify_one_per_group_strict : k_ed25519_verify_one_per_group)<<<(unsigned)n, 192, 0, stream>>>(
+            (zip215 ? k_ed25519_verify_one_per_group_zip215 : strict ? k_ed25519_verify_one_per_group_strict : k_ed25519_verify_one_per_group)<<<(unsigned)n, 192, 0, stream>>>(
                 fs, verdict, sig, pk, msgs, n, tbl);
             C25519_TRY(hipGetLastError());
         } else if (verify_quad_for(n)) {                   // four lanes per element walk; scalars and points side by side in one launch
             const unsigned sb = grid_for(n, FS_BLOCK);
-            (strict ? k_ed25519_verify_quad_prep_strict : k_ed25519_verify_quad_prep)<<<sb + grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
+            (zip215 ? k_ed25519_verify_quad_prep_zip215 : strict ? k_ed25519_verify_quad_prep_strict : k_ed25519_verify_quad_prep)<<<sb + grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
                 fs, sig, pk, msgs, n, sb);
             C25519_TRY(hipGetLastError());
-            (strict ? k_ed25519_verify_quad_walk_strict : k_ed25519_verify_quad_walk)<<<grid_for(n, QW_BLOCK / 4), QW_BLOCK, 0, stream>>>(
+            (zip215 ? k_ed25519_verify_quad_walk_zip215 : strict ? k_ed25519_verify_quad_walk_strict : k_ed25519_verify_quad_walk)<<<grid_for(n, QW_BLOCK / 4), QW_BLOCK, 0, stream>>>(
                 fs, verdict, n, tbl);
             C25519_TRY(hipGetLastError());
         } else {
-            (strict ? k_ed25519_verify_fast_scalars_strict : k_ed25519_verify_fast_scalars)<<<grid_for(n, FS_BLOCK), FS_BLOCK, 0, stream>>>(
+            (zip215 ? k_ed25519_verify_fast_scalars_zip215 : strict ? k_ed25519_verify_fast_scalars_strict : k_ed25519_verify_fast_scalars)<<<grid_for(n, FS_BLOCK), FS_BLOCK, 0, stream>>>(
                 fs, sig, pk, msgs, n);
             C25519_TRY(hipGetLastError());
-            if (strict)
+            if (zip215)
+                k_ed25519_verify_fast_points_zip215<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n, verdict);
+            else if (strict)
                 k_ed25519_verify_fast_points_strict<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n, verdict);
             else
                 k_ed25519_verify_fast_points<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(fs, sig, pk, n);
             C25519_TRY(hipGetLastError());
-            k_ed25519_verify_fast_walk<<<grid_for(n, WALK_BLOCK), WALK_BLOCK, 0, stream>>>(fs, verdict, n, tbl);   // (strict: rejected = listed)
+            // (strict, ZIP-215: rejected = listed; ZIP-215: the scalars came multiplied by 8, so the neutral test is the cofactored one)
+            k_ed25519_verify_fast_walk<<<grid_for(n, WALK_BLOCK), WALK_BLOCK, 0, stream>>>(fs, verdict, n, tbl);
             C25519_TRY(hipGetLastError());
         }
-        k_ed25519_verify_slow<<<grid, ED_BLOCK, 0, stream>>>(fs, verdict, sig, pk, msgs, tbl, take_done_word(n));
+        (zip215 ? k_ed25519_verify_slow_zip215 : k_ed25519_verify_slow)<<<grid, ED_BLOCK, 0, stream>>>(fs, verdict, sig, pk, msgs, tbl,
+                                                                                                     take_done_word(n));
         C25519_TRY(hipGetLastError());
         tl_last_verify.count = report; tl_last_verify.stream = stream;
         tl_last_verify.generation = tls().generation;       // the report word and the stream die with the thread's slabs
@@ -763,16 +924,17 @@ extern "C" {
 
 size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return verify_scratch_bytes(n); }
 
-static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, bool strict = false)
+static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream,
+                      VerifyRules rules = RULES_PLAIN)
 {
     // tunable VERIFY_REFERENCE_ORDER = 1: every element through the reference-order kernels -- Verify_Init's 4-fold table per
     // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob).
-    // The strict calls always take the lattice path: their rules live in its kernels.
-    const bool fast = strict || c25519_host::tunable_or(c25519_host::T_VERIFY_REFERENCE_ORDER, 0) == 0;
+    // The strict and the ZIP-215 calls always take the lattice path: their rules live in its kernels.
+    const bool fast = rules != RULES_PLAIN || c25519_host::tunable_or(c25519_host::T_VERIFY_REFERENCE_ORDER, 0) == 0;
     if (int rc = check_dev_args(n, { verdict, sig, pk })) return rc;
     if (n == 0) return 0;
     return verify_run(sig, pk, msgs, n, stream, (int*)verdict, fast,
-                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, strict);
+                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules);
 }
 
 // test hook: enc(T) instead of the verdict (what Verify_Check compares with enc(R)); device pointers
@@ -824,7 +986,7 @@ int ed25519_VerifySignature_strict_dev(void* verdict, const void* sig, const voi
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, true);
+    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, RULES_STRICT);
 }
 
 int ed25519_VerifySignature_strict_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
@@ -833,7 +995,25 @@ int ed25519_VerifySignature_strict_ragged_dev(void* verdict, const void* sig, co
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
     return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                      (hipStream_t)stream, true);
+                      (hipStream_t)stream, RULES_STRICT);
+}
+
+// the ZIP-215 verdict (include/curve25519_amd.h): same arguments, dispatch and tunables as ed25519_VerifySignature_dev
+int ed25519_VerifySignature_zip215_dev(void* verdict, const void* sig, const void* pk, const void* msg, size_t msg_size,
+                                       size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
+    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, RULES_ZIP215);
+}
+
+int ed25519_VerifySignature_zip215_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
+                                              const uint64_t* offsets, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
+    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
+                      (hipStream_t)stream, RULES_ZIP215);
 }
 
 // two-phase verification on the device: contexts are 2080-byte records (pk || 16 x 128-byte canonical rows),

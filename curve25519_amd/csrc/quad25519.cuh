@@ -293,6 +293,8 @@ C25519_DEV void comb_field(fe& mult, const u32* tbl, u32 c, const Roles& R)
 // starts from the neutral element (one more addition than the one-lane walk's "first row as the starting point").
 // q_flip (all-ones or zero): the table at tq holds the point as decoded and the walk wants its negative (tau < 0: the rows'
 // signs flip, nothing else -- the points were decoded and tabulated beside the scalar work, before tau's sign was known).
+// Cofactored (the ZIP-215 calls): all-ones iff [8]W is the neutral element -- three doublings in front of the test.
+template <bool Cofactored = false>
 C25519_DEV u32 walk_is_neutral(const WalkScalars& sc, const u32* tq, const u32* tr, const u32* lds_tbl, int top, const Roles& R,
                                u32 q_flip = 0)
 {
@@ -338,6 +340,10 @@ C25519_DEV u32 walk_is_neutral(const WalkScalars& sc, const u32* tq, const u32* 
         ge_add_fields(own, mult, R);
         row_field_unpack(mult, rr, R);
         ge_add_fields(own, mult, R);
+    }
+    if (Cofactored) {
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) ge_double(own, R);
     }
     // neutral element: X == 0 and Y == Z (Z != 0 for on-curve inputs under the complete law)
     fe X, Y, Z, d;

@@ -859,6 +859,36 @@ C25519_DEV u32 ed_verify_fast_scalars(u32 (&sigma_cols)[SIGMA_WORDS], u32 (&rho)
     return lat_ok;
 }
 
+// step 1 for the ZIP-215 calls.  scale8 = false: ed_verify_fast_scalars as it is (the quad and per-wave walks double their sum three
+// times themselves).  scale8 = true, the lane path: the three scalars come back multiplied by 8 -- sigma = 8 rho s mod L, 8 tau,
+// 8 rho -- so that the PLAIN walk's sum is [8 rho](S*B - k*A - R) and its neutral test is the cofactored one (a twin of the walk
+// kernel with three doublings in it changed the plain walk kernel's gfx950 code, which must stay what it was).  Three more bits:
+// the vector has to fit cap_bits - 3, and a wave starts 0.75 digit rounds higher on average.
+C25519_DEV u32 ed_verify_zip215_scalars(u32 (&sigma_cols)[SIGMA_WORDS], u32 (&rho)[5], u32 (&tau)[5], u32& tau_negative, const u32 (&pkw)[8],
+                                        const u32 (&Rw)[8], const u32 (&Sw)[8], const uint8_t* msg, size_t len, int cap_bits, bool scale8)
+{
+    if (!scale8) return ed_verify_fast_scalars(sigma_cols, rho, tau, tau_negative, pkw, Rw, Sw, msg, len, cap_bits);
+    u32 h[8], sigma[8];
+    ed_hram(h, Rw, pkw, msg, len);
+    sc_mod(h);
+    const u32 lat_ok = sc_lattice_short(rho, tau, tau_negative, h, cap_bits - 3);
+#pragma unroll
+    for (int i = 4; i >= 0; i--) {                           // below 2^158 where lat_ok; used nowhere where not
+        rho[i] = (rho[i] << 3) | (i ? rho[i - 1] >> 29 : 0u);
+        tau[i] = (tau[i] << 3) | (i ? tau[i - 1] >> 29 : 0u);
+    }
+    sc_mul_short(sigma, rho, Sw);
+    sc_comb_columns(sigma_cols, sigma);
+    u32 b[5];
+    bias_signed16(b, rho);
+#pragma unroll
+    for (int i = 0; i < 5; i++) rho[i] = b[i];
+    bias_signed16(b, tau);
+#pragma unroll
+    for (int i = 0; i < 5; i++) tau[i] = b[i];
+    return lat_ok;
+}
+
 // step 2, one point per call (the kernel gives the key and R of an element to two different lanes): y from the 32 bytes
 // with bit 255 stripped, x with the requested parity.
 //   is_r = 0:       the key A, decoded as -A exactly as ed25519_Verify_Init does (inverted parity, :191-197), and negated
@@ -889,6 +919,66 @@ C25519_DEV u32 ed_verify_fast_decode(fe& X, fe& Y, const u32 (&w)[8], u32 is_r, 
     fe_carry32(t, t);
     fe_select(X, is_r | tau_negative, t, X);
     return ok;
+}
+
+// step 2 under the ZIP-215 rule (ed25519_VerifySignature_zip215_*), for the key and for R alike: y = the low 255 bits taken mod p
+// (every value below 2^255 is accepted: the field arithmetic reduces it), x = the square root with the parity of bit 255, and
+// x = 0 whatever that bit says.  No canonical-encoding term.  The point comes back negated where `negate` is all-ones: R always
+// (the walk adds rho * (-R)), the key unless tau < 0 (the walk uses |tau| on -A).  Returns all-ones iff there is a square root.
+C25519_DEV u32 ed_zip215_decode(fe& X, fe& Y, const u32 (&w)[8], u32 negate)
+{
+    u32 yw[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) yw[i] = w[i];
+    const u32 sign = yw[7] >> 31;
+    yw[7] &= 0x7fffffffu;
+    fe_from_words(Y, yw);
+    const u32 ok = ge_calc_x_checked(X, Y, sign);
+    fe t;
+    fe_neg(t, X);
+    fe_carry32(t, t);
+    fe_select(X, negate, t, X);
+    return ok;
+}
+
+// The ZIP-215 verdict for one element in the reference's order of operations, for an element whose lattice vector does not fit
+// the walk (its key is on the curve: a key that is not was rejected where it was decoded).  T = S*B + h*(-A) as
+// ed_verify_reference_order forms it -- on the curve that is the group's T whatever the order -- and [8](T - R) = O is tested as
+// [8]T == [8]R: three doublings each (they do not read the coordinate T, which the walk's last addition leaves out) and a
+// projective comparison (Z != 0 under the complete law).  lane_table: 16 packed rows.  Sw is consumed.
+C25519_DEV int ed_verify_zip215_reference_order(const u32 (&pkw)[8], const u32 (&Rw)[8], u32 (&Sw)[8], const uint8_t* msg, size_t len,
+                                                u32* lane_table, const u32* lds_tbl)
+{
+    u32 h[8];
+    {
+        ge_ext Q;
+        ed_decode_neg_key(Q, pkw);
+        qtable_build_streamed(lane_table, Q);
+    }
+    ed_hram(h, Rw, pkw, msg, len);
+    sc_mod(h);
+    ge_ext T;
+    ge_poly_mult_streamed(T, Sw, h, lane_table, lds_tbl);
+#pragma unroll 1
+    for (int j = 0; j < 3; j++) ge_double<false>(T);
+    ge_ext R;
+    const u32 r_ok = ed_zip215_decode(R.X, R.Y, Rw, 0u);
+    fe_set_u32(R.Z, 1);
+#pragma unroll 1
+    for (int j = 0; j < 3; j++) ge_double<false>(R);
+    fe a, b;
+    u32 aw[8], bw[8], acc = 0;
+    fe_mul(a, T.X, R.Z);
+    fe_mul(b, R.X, T.Z);
+    fe_sub(a, a, b);
+    fe_to_words(aw, a);
+    fe_mul(a, T.Y, R.Z);
+    fe_mul(b, R.Y, T.Z);
+    fe_sub(a, a, b);
+    fe_to_words(bw, a);
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc |= aw[i] | bw[i];
+    return (acc == 0 && r_ok) ? 1 : 0;
 }
 
 // step 3: wtable_build above, once per point (the kernel gives the two tables of an element to two different lanes).

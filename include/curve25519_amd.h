@@ -262,6 +262,47 @@ int ed25519_VerifySignature_strict_ragged_batch(int *verdict, const unsigned cha
 int ed25519_VerifySignature_strict_ragged_dev(void *verdict, const void *sig, const void *pk, const void *msgs,
                                               const uint64_t *offsets, size_t n, void *stream);
 
+/* ZIP-215 verification: the rule a consensus verifier implements to the bit (Zcash since Canopy, ed25519-zebra,
+ * ed25519-consensus) -- the cofactored equation, every point encoding that decodes, only S canonical.  Read S = sig[32..63] as a
+ * 256-bit little-endian integer.  Decode a 32-byte string E as: sign = bit 255, y = the low 255 bits reduced mod p (all of
+ * [p, 2^255) accepted), x = the square root of (y^2 - 1) / (d y^2 + 1) with parity sign; decoding fails only when there is no
+ * square root, and x = 0 with sign = 1 decodes to x = 0.  The verdict is 1 exactly when
+ *   1. S < L;
+ *   2. the key bytes decode to a curve point A;
+ *   3. sig[0..31] decodes to a curve point R;
+ *   4. [8]([S]B - [k]A - R) is the neutral element, k = SHA-512(sig[0..31] || pk || msg) mod L over the bytes as given.
+ * No small-order or canonical-encoding rule applies to A or R.  Single and batched verification cannot disagree under this rule.
+ *
+ *                          plain (reference)        OpenSSL 3.0              strict (libsodium)       ZIP-215
+ *   S >= L                 accepted (S + L too)     rejected                 rejected                 rejected
+ *   small-order A          accepted                 accepted                 rejected                 accepted
+ *   small-order R          accepted if canonical    accepted if canonical    rejected                 accepted, any encoding
+ *   y >= p                 key: y mod p; R: never   key: y mod p; R: never   rejected                 accepted: y mod p
+ *   x = 0 with sign bit    key: x = 0; R: never     key: x = 0; R: never     rejected (small order)   accepted: x = 0
+ *   key off the curve      taken as it is           rejected                 rejected                 rejected
+ *   mixed-order key        when h*t + j = 0 mod 8   when h*t + j = 0 mod 8   when h*t + j = 0 mod 8   whenever the signature is right
+ *   torsion-shifted R      when h*t + j = 0 mod 8   when h*t + j = 0 mod 8   when h*t + j = 0 mod 8   accepted
+ * (A = a*B + t*T8, R = r*B + j*T8, S = r + h*a; "R: never": the byte comparison with enc(T) cannot succeed.)
+ *
+ * The lattice path does not compare encodings: it walks W = [rho]([S]B - [k]A - R) with rho odd, and multiplication by rho is a
+ * bijection of the group that maps the 8-torsion onto itself, so [8]W = O is rule 4: the plain walk, three doublings, the same
+ * neutral test ("ZIP-215 verification"; calls above 2^15 elements hand the plain walk kernel scalars multiplied by 8
+ * instead).  S >= L, a key or an R that does not decode get verdict 0 where they are
+ * decoded and go to no other kernel; an element whose lattice vector does not fit the walk (practically never) is decided by a
+ * cofactored reference-order kernel, and c25519_amd_verify_last_slow_elements counts only those.  The tunable
+ * VERIFY_REFERENCE_ORDER does not apply.  Argument rules, layouts, dispatch (COOP_MAX, QUAD_MIN / QUAD_MAX) and stream behaviour
+ * are ed25519_VerifySignature_*'s.  Rate against the plain call of the same build on the same honest inputs
+ * (profiles/verify_zip215_rate.txt): 0.998 x at 2^10, 0.967 at 2^12, 0.975 at 2^14, 1.001 at 2^16, 0.987 at 2^20 (110.3 M/s); a single
+ * call 127.9 us (plain 128.2); at 2^20, every second key off the curve 0.95 x the honest time, every R of small order 0.99 x. */
+int ed25519_VerifySignature_zip215_batch(int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                         const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_VerifySignature_zip215_dev(void *verdict, const void *sig, const void *pk, const void *msg,
+                                       size_t msg_size, size_t n, void *stream);
+int ed25519_VerifySignature_zip215_ragged_batch(int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                                const unsigned char *msgs, const uint64_t *offsets, size_t n);
+int ed25519_VerifySignature_zip215_ragged_dev(void *verdict, const void *sig, const void *pk, const void *msgs,
+                                              const uint64_t *offsets, size_t n, void *stream);
+
 /* ed25519_VerifySignature_* decide every element whose key decompresses onto the curve with an exact
  * lattice-shortened walk (csrc/verify_fast.cuh, ~134 doublings instead of 255) and run the reference's own operation
  * order only for the others (set C25519_AMD_VERIFY_REFERENCE_ORDER=1 to force it for everything).  This reports how many
