@@ -80,10 +80,7 @@ def curve25519_dh_CreateSharedKey_indexed(ctxs, idx, sk):
     element i against the key of context idx[i] as curve25519_dh_CreateSharedKey would.  An index >= n_ctx raises EngineError."""
     sk = np.array(_np(sk, 32, "sk"), copy=True)
     n = sk.shape[0]
-    ctxs = _np(ctxs, PEER_CTX_SIZE, "ctxs") if np.size(ctxs) else np.zeros((0, PEER_CTX_SIZE), np.uint8)
-    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
-    if idx.size != n:
-        raise ValueError("one context index per secret")
+    ctxs, idx = _ctx_index(ctxs, idx, n, PEER_CTX_SIZE, "secret")
     out = np.empty_like(sk)
     _lib.check(_lib.load().curve25519_dh_CreateSharedKey_indexed_batch(_ptr(out), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sk), n),
                "curve25519_dh_CreateSharedKey_indexed_batch")
@@ -181,7 +178,11 @@ def ed25519_SignMessage_indexed_ragged(ctxs, idx, messages):
     return sig
 
 
-def ed25519_VerifySignature_ragged(sig, pk, messages, strict=False):
+# the verification rule sets (include/curve25519_amd.h): what goes between "ed25519_VerifySignature_" and the form's suffix
+_RULES = {"plain": "", "strict": "strict_", "zip215": "zip215_"}
+
+
+def _verify_ragged(sig, pk, messages, rules):
     sig = _np(sig, 64, "sig")
     pk = _np(pk, 32, "pk")
     n = sig.shape[0]
@@ -189,63 +190,53 @@ def ed25519_VerifySignature_ragged(sig, pk, messages, strict=False):
         raise ValueError("one message and one key per signature")
     flat, offsets = _ragged(messages)
     ok = np.empty(n, np.int32)
-    name = "ed25519_VerifySignature_strict_ragged_batch" if strict else "ed25519_VerifySignature_ragged_batch"
+    name = f"ed25519_VerifySignature_{_RULES[rules]}ragged_batch"
     _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(flat), _ptr(offsets), n), name)
     return ok
 
 
+def ed25519_VerifySignature_ragged(sig, pk, messages, strict=False):
+    return _verify_ragged(sig, pk, messages, "strict" if strict else "plain")
+
+
 def ed25519_VerifySignature_strict_ragged(sig, pk, messages):
     """ed25519_VerifySignature_strict with per-element message lengths (`messages`: sequence of bytes-like)."""
-    return ed25519_VerifySignature_ragged(sig, pk, messages, strict=True)
+    return _verify_ragged(sig, pk, messages, "strict")
+
+
+def _verify(sig, pk, msg, rules):
+    sig = _np(sig, 64, "sig")
+    pk = _np(pk, 32, "pk")
+    n = sig.shape[0]
+    if pk.shape[0] != n:
+        raise ValueError("sig and pk must have the same number of rows")
+    msg, msg_size = _msgs(msg, n)
+    ok = np.empty(n, np.int32)
+    name = f"ed25519_VerifySignature_{_RULES[rules]}batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n), name)
+    return ok
 
 
 def ed25519_VerifySignature_strict(sig, pk, msg):
     """n x strict verification (include/curve25519_amd.h: rules 1-6 -- S < L, a canonical key on the curve and not of small order,
     R not of small order, and the reference's verdict).  Returns int32[n] of 1 (valid) / 0 (invalid or rejected)."""
-    return ed25519_VerifySignature(sig, pk, msg, strict=True)
+    return _verify(sig, pk, msg, "strict")
 
 
 def ed25519_VerifySignature(sig, pk, msg, strict=False):
     """n x ed25519_VerifySignature.  Returns int32[n] of 1 (valid) / 0 (invalid)."""
-    sig = _np(sig, 64, "sig")
-    pk = _np(pk, 32, "pk")
-    n = sig.shape[0]
-    if pk.shape[0] != n:
-        raise ValueError("sig and pk must have the same number of rows")
-    msg, msg_size = _msgs(msg, n)
-    ok = np.empty(n, np.int32)
-    name = "ed25519_VerifySignature_strict_batch" if strict else "ed25519_VerifySignature_batch"
-    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n), name)
-    return ok
+    return _verify(sig, pk, msg, "strict" if strict else "plain")
 
 
 def ed25519_VerifySignature_zip215(sig, pk, msg):
     """n x ZIP-215 verification (include/curve25519_amd.h: S < L, key and R in any encoding that decodes, the cofactored equation
     [8]([S]B - [k]A - R) = O).  Returns int32[n] of 1 (valid) / 0 (invalid)."""
-    sig = _np(sig, 64, "sig")
-    pk = _np(pk, 32, "pk")
-    n = sig.shape[0]
-    if pk.shape[0] != n:
-        raise ValueError("sig and pk must have the same number of rows")
-    msg, msg_size = _msgs(msg, n)
-    ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_VerifySignature_zip215_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(msg), msg_size, n),
-               "ed25519_VerifySignature_zip215_batch")
-    return ok
+    return _verify(sig, pk, msg, "zip215")
 
 
 def ed25519_VerifySignature_zip215_ragged(sig, pk, messages):
     """ed25519_VerifySignature_zip215 with per-element message lengths (`messages`: sequence of bytes-like)."""
-    sig = _np(sig, 64, "sig")
-    pk = _np(pk, 32, "pk")
-    n = sig.shape[0]
-    if len(messages) != n or pk.shape[0] != n:
-        raise ValueError("one message and one key per signature")
-    flat, offsets = _ragged(messages)
-    ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_VerifySignature_zip215_ragged_batch(_ptr(ok), _ptr(sig), _ptr(pk), _ptr(flat), _ptr(offsets), n),
-               "ed25519_VerifySignature_zip215_ragged_batch")
-    return ok
+    return _verify_ragged(sig, pk, messages, "zip215")
 
 
 def ed25519_Verify_Init(pk):
@@ -449,29 +440,28 @@ def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):
         _lib.check(_lib.load().ed25519_Verify_Check_indexed_dev(*args, msg.shape[1], n, st), "ed25519_Verify_Check_indexed_dev")
 
 
-def ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=False):
+def _verify_dev(verdict, sig, pk, msg, rules):
     import torch
     n, d = sig.shape[0], sig.device
     args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
             _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
-    name = "ed25519_VerifySignature_strict_dev" if strict else "ed25519_VerifySignature_dev"
+    name = f"ed25519_VerifySignature_{_RULES[rules]}dev"
     with _on(sig) as st:
         _lib.check(getattr(_lib.load(), name)(*args, msg.shape[1], n, st), name)
 
 
+def ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=False):
+    _verify_dev(verdict, sig, pk, msg, "strict" if strict else "plain")
+
+
 def ed25519_VerifySignature_strict_dev(verdict, sig, pk, msg):
     """Device form of ed25519_VerifySignature_strict: verdict int32[n, 1]."""
-    ed25519_VerifySignature_dev(verdict, sig, pk, msg, strict=True)
+    _verify_dev(verdict, sig, pk, msg, "strict")
 
 
 def ed25519_VerifySignature_zip215_dev(verdict, sig, pk, msg):
     """Device form of ed25519_VerifySignature_zip215: verdict int32[n, 1]."""
-    import torch
-    n, d = sig.shape[0], sig.device
-    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
-            _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
-    with _on(sig) as st:
-        _lib.check(_lib.load().ed25519_VerifySignature_zip215_dev(*args, msg.shape[1], n, st), "ed25519_VerifySignature_zip215_dev")
+    _verify_dev(verdict, sig, pk, msg, "zip215")
 
 
 def ed25519_Verify_Check_strict_dev(verdict, ctx, sig, msg):

@@ -215,6 +215,58 @@ inline void arm_exit_guard()
         });
 }
 
+// The two kinds of per-thread device copy of caller data that outlive a *_batch call (ThreadState below).  Both are zeroed before
+// they go back to the allocator, public keys included: one rule for all of them.
+// A fixed-size record the caller passes again and again (one Verify_Init and many Verify_Check calls, ed25519_verify.c:282-286;
+// one blinding context, one peer key): uploaded only when its bytes differ from what the thread uploaded last -- a memcmp against
+// a synchronous ~12 us copy per call.
+template <size_t BYTES>
+struct KeptRecord {
+    void* dev = nullptr;
+    unsigned char host[BYTES] = {};        // the bytes that were uploaded into dev
+    bool valid = false;
+    int device_copy(void** out, const void* bytes)
+    {
+        if (!dev) C25519_TRY(hipMalloc(&dev, BYTES));
+        if (!valid || memcmp(host, bytes, BYTES) != 0) {
+            valid = false;
+            C25519_RC(upload_now(dev, bytes, BYTES));
+            memcpy(host, bytes, BYTES);
+            valid = true;
+        }
+        *out = dev;
+        return 0;
+    }
+    void release()                         // on the record's device, after a synchronize
+    {
+        if (dev) { (void)zero_device_now(dev, BYTES); (void)hipFree(dev); }
+        memset(host, 0, sizeof host);
+        dev = nullptr; valid = false;
+    }
+};
+// The contexts of an indexed call: a grow-only array, uploaded on every call.
+struct GrowArray {
+    void* dev = nullptr;
+    size_t cap = 0;
+    int upload(void** out, const void* src, size_t bytes)
+    {
+        if (bytes > cap) {
+            if (dev) { C25519_RC(zero_device_now(dev, cap)); C25519_TRY(hipFree(dev)); }
+            dev = nullptr; cap = 0;
+            C25519_TRY(hipMalloc(&dev, bytes));
+            cap = bytes;
+        }
+        C25519_RC(upload_now(dev, src, bytes));
+        *out = dev;
+        return 0;
+    }
+    void release()
+    {
+        if (dev) { (void)zero_device_now(dev, cap); (void)hipFree(dev); }
+        dev = nullptr; cap = 0;
+    }
+};
+
 // Per-host-thread device resources.  The staging side (streams, pinned + device buffers of the *_batch pipeline)
 // belongs to ONE device (`device`): when the thread calls a *_batch function with another current device, the old
 // device's staging is released first, on that device.  Work scratch of the *_dev functions is kept per device.
@@ -233,21 +285,13 @@ struct ThreadState {
     hipEvent_t computed[SETS] = {};        // end of a set's last kernels
     void* dbuf[SETS][SLOTS] = {};          // device staging
     size_t dcap[SETS][SLOTS] = {};
-    void* vctx = nullptr;                  // the 2080-byte context of this thread's last ed25519_Verify_Check_batch (nothing else writes it)
-    unsigned char vctx_host[2080] = {};    // ... and the bytes that were uploaded into it
-    bool vctx_valid = false;
-    void* vctxs = nullptr;                 // the n_ctx x 2080 bytes of this thread's last ed25519_Verify_Check_indexed_*batch (grow-only)
-    size_t vctxs_cap = 0;
-    void* pctxs = nullptr;                 // the n_ctx x 1600 bytes of this thread's last curve25519_dh_CreateSharedKey_indexed_batch (grow-only)
-    size_t pctxs_cap = 0;
-    void* sctxs = nullptr;                 // the n_ctx x 128 bytes of this thread's last ed25519_SignMessage_indexed_*batch (grow-only; secret)
-    size_t sctxs_cap = 0;
-    void* bctx = nullptr;                  // the same for the 192-byte blinding context of this thread's last blinded *_batch call
-    unsigned char bctx_host[192] = {};
-    bool bctx_valid = false;
-    void* peer = nullptr;                  // ... and for the 32-byte peer key of this thread's last one-peer X25519 *_batch call
-    unsigned char peer_host[32] = {};
-    bool peer_valid = false;
+    // this thread's copies of what its last calls were given (KeptRecord, GrowArray above): the 2080-byte context of
+    // ed25519_Verify_Check_*batch, the 192-byte blinding context, the one-peer call's key; the n_ctx x 2080 / 1600 / 128 bytes of the
+    // indexed verification, X25519 and signing calls (the last are secret)
+    KeptRecord<2080> vctx;
+    KeptRecord<192> bctx;
+    KeptRecord<32> peer;
+    GrowArray vctxs, pctxs, sctxs;
     void* hbuf[SETS][SLOTS] = {};          // pinned host staging (hipHostMalloc)
     size_t hcap[SETS][SLOTS] = {};
     // The completion word of a call of ONE element (host_pipeline.hpp: zero-copy calls): pinned host memory the call's last
@@ -465,19 +509,8 @@ struct ThreadState {
         }
         if (done_word) { (void)hipHostFree(done_word); done_word = nullptr; }
         done_offered = done_taken = false;
-        if (vctx) { (void)hipMemset(vctx, 0, 2080); (void)hipFree(vctx); vctx = nullptr; }
-        vctx_valid = false;
-        if (vctxs) { (void)hipMemset(vctxs, 0, vctxs_cap); (void)hipFree(vctxs); vctxs = nullptr; }
-        vctxs_cap = 0;
-        if (pctxs) { (void)hipMemset(pctxs, 0, pctxs_cap); (void)hipFree(pctxs); pctxs = nullptr; }
-        pctxs_cap = 0;
-        if (sctxs) { (void)hipMemset(sctxs, 0, sctxs_cap); (void)hipFree(sctxs); sctxs = nullptr; }
-        sctxs_cap = 0;
-        if (bctx) { (void)hipMemset(bctx, 0, 192); (void)hipFree(bctx); bctx = nullptr; }
-        memset(bctx_host, 0, sizeof bctx_host);
-        bctx_valid = false;
-        if (peer) { (void)hipFree(peer); peer = nullptr; }
-        peer_valid = false;
+        vctx.release(); bctx.release(); peer.release();
+        vctxs.release(); pctxs.release(); sctxs.release();
         for (int l = 0; l < LANES; l++) {
             free_slab(lane_work[l]);
             if (stream[l]) (void)hipStreamDestroy(stream[l]);

@@ -312,14 +312,8 @@ int curve25519_dh_CreateSharedKey_one_peer_batch(unsigned char* shared, const un
     if (n == 0) return 0;
     ThreadState& t = tls();
     C25519_RC(t.ensure());
-    if (!t.peer) C25519_TRY(hipMalloc(&t.peer, 32));
-    void* dpk = t.peer;
-    if (!t.peer_valid || memcmp(t.peer_host, pk, 32) != 0) {
-        t.peer_valid = false;
-        C25519_RC(c25519_host::upload_now(dpk, pk, 32));
-        memcpy(t.peer_host, pk, 32);
-        t.peer_valid = true;
-    }
+    void* dpk = nullptr;
+    C25519_RC(t.peer.device_copy(&dpk, pk));
     return run_batch(n, { Arr{ sk, sk, 32 }, Arr{ nullptr, shared, 32 } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
                          return curve25519_dh_CreateSharedKey_one_peer_dev(d[1], dpk, d[0], c, st);
@@ -336,30 +330,28 @@ int curve25519_dh_Peer_Init_batch(void* ctx, const unsigned char* pk, size_t n)
                      });
 }
 
-// many peer contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
-// uploaded once per call into a grow-only device buffer of the calling thread, the indices travel in pieces with the secrets
+// many contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
+// uploaded once per call into a grow-only device buffer of the calling thread (`kept`: the peer, the verification or the signer
+// contexts'), the indices travel with the elements
+static int indexed_prepare(void** dctxs, c25519_host::GrowArray& kept, size_t ctx_bytes, const void* ctxs, size_t n_ctx,
+                           const uint32_t* ctx_index, size_t n)
+{
+    if (n_ctx == 0) return bad_arg("no contexts");
+    if (n_ctx > ((size_t)1 << 32)) return bad_arg("more contexts than a uint32 index reaches");
+    for (size_t i = 0; i < n; i++)
+        if (ctx_index[i] >= n_ctx) return bad_arg("context index out of range");
+    C25519_RC(tls().ensure());
+    return kept.upload(dctxs, ctxs, n_ctx * ctx_bytes);
+}
+
 int curve25519_dh_CreateSharedKey_indexed_batch(unsigned char* shared, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                                 unsigned char* sk, size_t n)
 {
     C25519_API_CALL();
     if (!shared || !ctxs || !ctx_index || !sk) return bad_arg("null pointer");
     if (n == 0) return 0;
-    if (n_ctx == 0) return bad_arg("no contexts");
-    if (n_ctx > ((size_t)1 << 32)) return bad_arg("more contexts than a uint32 index reaches");
-    for (size_t i = 0; i < n; i++)
-        if (ctx_index[i] >= n_ctx) return bad_arg("context index out of range");
-    ThreadState& t = tls();
-    C25519_RC(t.ensure());
-    const size_t bytes = n_ctx * 1600;
-    if (bytes > t.pctxs_cap) {
-        if (t.pctxs) { C25519_TRY(hipMemset(t.pctxs, 0, t.pctxs_cap)); C25519_TRY(hipFree(t.pctxs)); }
-        t.pctxs = nullptr;
-        t.pctxs_cap = 0;
-        C25519_TRY(hipMalloc(&t.pctxs, bytes));
-        t.pctxs_cap = bytes;
-    }
-    C25519_RC(c25519_host::upload_now(t.pctxs, ctxs, bytes));
-    void* dctxs = t.pctxs;
+    void* dctxs = nullptr;
+    C25519_RC(indexed_prepare(&dctxs, tls().pctxs, 1600, ctxs, n_ctx, ctx_index, n));
     return run_batch(n, { Arr{ sk, sk, 32 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ nullptr, shared, 32 } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
                          return curve25519_dh_CreateSharedKey_indexed_dev(d[2], dctxs, n_ctx, d[1], d[0], c, st);
@@ -387,15 +379,8 @@ static int upload_blinding(void** dctx, const void* blinding)
     C25519_RC(t.ensure());
     // a caller signs many times with one context (the reference's C++ wrapper keeps two static ones, C++/ed25519.cpp): it
     // is uploaded when its bytes differ from what this thread uploaded last, not with a synchronous copy per call
-    if (!t.bctx) C25519_TRY(hipMalloc(&t.bctx, 4 * BLIND_WORDS));
-    if (!t.bctx_valid || memcmp(t.bctx_host, blinding, 4 * BLIND_WORDS) != 0) {
-        t.bctx_valid = false;
-        C25519_RC(c25519_host::upload_now(t.bctx, blinding, 4 * BLIND_WORDS));
-        memcpy(t.bctx_host, blinding, 4 * BLIND_WORDS);
-        t.bctx_valid = true;
-    }
-    *dctx = t.bctx;
-    return 0;
+    static_assert(sizeof t.bctx.host == 4 * BLIND_WORDS, "the kept blinding record is one context");
+    return t.bctx.device_copy(dctx, blinding);
 }
 
 static int keypair_batch(unsigned char* pub, unsigned char* priv, const void* blinding, const unsigned char* sk, size_t n)
@@ -433,7 +418,7 @@ static int sign_batch(unsigned char* sig, const unsigned char* priv, const void*
     if (blinding) C25519_RC(upload_blinding(&dctx, blinding));
     return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, sig, 64 } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return sign_dev(d[2], d[0], dctx, Msgs{ (const uint8_t*)d[1], msg_size, nullptr }, c, st);
+                         return sign_dev(d[2], d[0], dctx, fixed_msgs(d[1], msg_size), c, st);
                      });
 }
 
@@ -450,115 +435,74 @@ int ed25519_SignMessage_blinded_batch(unsigned char* sig, const unsigned char* p
     return sign_batch(sig, priv, blinding, msg, msg_size, n);
 }
 
-// rules: 0 the plain call, 1 strict, 2 ZIP-215
 static int verify_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msg, size_t msg_size,
-                        size_t n, int rules)
+                        size_t n, VerifyRules rules)
 {
-    const auto dev = rules == 2 ? ed25519_VerifySignature_zip215_dev : rules == 1 ? ed25519_VerifySignature_strict_dev : ed25519_VerifySignature_dev;
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ pk, nullptr, 32 }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return dev(d[3], d[0], d[1], d[2], msg_size, c, st);
+                         return verify_dev(d[3], d[0], d[1], fixed_msgs(d[2], msg_size), c, st, rules);
                      });
 }
 
 int ed25519_VerifySignature_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                   const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, 0);
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_PLAIN);
 }
 
 int ed25519_VerifySignature_strict_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, 1);
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_STRICT);
 }
 
 int ed25519_VerifySignature_zip215_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, 2);
+    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_ZIP215);
 }
 
-// ragged messages: message i is msgs[offsets[i] .. offsets[i+1]); offsets has n+1 entries (host memory).
-// One piece: the message bytes and the offsets are uploaded whole.
-static int ragged_upload(ThreadState& t, void** d_msgs, void** d_off, const unsigned char* msgs, const uint64_t* offsets,
-                         size_t n)
-{
-    const int L = ThreadState::LANES - 1;
-    C25519_RC(t.reserve_dev(L, 3, (size_t)offsets[n]));
-    C25519_RC(t.reserve_dev(L, 4, sizeof(uint64_t) * (n + 1)));
-    *d_msgs = t.dbuf[L][3];
-    *d_off = t.dbuf[L][4];
-    if (offsets[n]) C25519_TRY(hipMemcpyAsync(*d_msgs, msgs, (size_t)offsets[n], hipMemcpyHostToDevice, t.stream[L]));
-    C25519_TRY(hipMemcpyAsync(*d_off, offsets, sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, t.stream[L]));
-    return 0;
-}
-
+// ragged messages (host_pipeline.hpp: run_ragged)
 int ed25519_SignMessage_ragged_batch(unsigned char* sig, const unsigned char* priv, const unsigned char* msgs,
                                      const uint64_t* offsets, size_t n)
 {
     C25519_API_CALL();
     if (!sig || !priv || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(t.ensure());
-    const int L = ThreadState::LANES - 1;
-    hipStream_t st = t.stream[L];
-    void *d_msgs, *d_off;
-    C25519_RC(ragged_upload(t, &d_msgs, &d_off, msgs, offsets, n));
-    C25519_RC(t.reserve_dev(L, 0, 64 * n));
-    C25519_RC(t.reserve_dev(L, 1, 64 * n));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], priv, 64 * n, hipMemcpyHostToDevice, st));
-    C25519_RC(ed25519_SignMessage_ragged_dev(t.dbuf[L][1], t.dbuf[L][0], d_msgs, (const uint64_t*)d_off, n, st));
-    C25519_TRY(hipMemcpyAsync(sig, t.dbuf[L][1], 64 * n, hipMemcpyDeviceToHost, st));
-    C25519_TRY(hipStreamSynchronize(st));
-    return 0;
+    return run_ragged(n, { Arr{ priv, nullptr, 64 }, Arr{ nullptr, sig, 64 } }, msgs, offsets, [&](void** d, hipStream_t st) -> int {
+        return sign_dev(d[1], d[0], nullptr, ragged_msgs(d[2], d[3]), n, st);
+    });
 }
 
 static int verify_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msgs,
-                               const uint64_t* offsets, size_t n, int rules)
+                               const uint64_t* offsets, size_t n, VerifyRules rules)
 {
-    const auto dev = rules == 2 ? ed25519_VerifySignature_zip215_ragged_dev
-                     : rules == 1 ? ed25519_VerifySignature_strict_ragged_dev : ed25519_VerifySignature_ragged_dev;
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(t.ensure());
-    const int L = ThreadState::LANES - 1;
-    hipStream_t st = t.stream[L];
-    void *d_msgs, *d_off;
-    C25519_RC(ragged_upload(t, &d_msgs, &d_off, msgs, offsets, n));
-    C25519_RC(t.reserve_dev(L, 0, 64 * n));
-    C25519_RC(t.reserve_dev(L, 1, 32 * n));
-    C25519_RC(t.reserve_dev(L, 2, sizeof(int) * n));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], sig, 64 * n, hipMemcpyHostToDevice, st));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][1], pk, 32 * n, hipMemcpyHostToDevice, st));
-    C25519_RC(dev(t.dbuf[L][2], t.dbuf[L][0], t.dbuf[L][1], d_msgs, (const uint64_t*)d_off, n, st));
-    C25519_TRY(hipMemcpyAsync(verdict, t.dbuf[L][2], sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    C25519_TRY(hipStreamSynchronize(st));
-    return 0;
+    return run_ragged(n, { Arr{ sig, nullptr, 64 }, Arr{ pk, nullptr, 32 }, Arr{ nullptr, verdict, sizeof(int) } }, msgs, offsets,
+                      [&](void** d, hipStream_t st) -> int { return verify_dev(d[2], d[0], d[1], ragged_msgs(d[3], d[4]), n, st, rules); });
 }
 
 int ed25519_VerifySignature_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msgs, const uint64_t* offsets, size_t n)
 {
-    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 0);
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, RULES_PLAIN);
 }
 
 int ed25519_VerifySignature_strict_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                                 const unsigned char* msgs, const uint64_t* offsets, size_t n)
 {
-    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 1);
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, RULES_STRICT);
 }
 
 int ed25519_VerifySignature_zip215_ragged_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                                 const unsigned char* msgs, const uint64_t* offsets, size_t n)
 {
-    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, 2);
+    return verify_ragged_batch(verdict, sig, pk, msgs, offsets, n, RULES_ZIP215);
 }
 
 // ---- the reference's single-call API: a device batch of one, fatal on device failure --------------
@@ -637,62 +581,33 @@ int ed25519_Verify_Init_batch(void* ctx, const unsigned char* pk, size_t n)
 }
 
 static int verify_check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg, size_t msg_size,
-                              size_t n, bool strict)
+                              size_t n, VerifyRules rules)
 {
     C25519_API_CALL();
     if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    if (rules == RULES_ZIP215) return bad_arg("internal: ed25519_Verify_Check has no ZIP-215 form");
     if (n == 0) return 0;
     ThreadState& t = tls();
     C25519_RC(t.ensure());
-    // the reference's two-phase use is one Verify_Init and MANY Verify_Check calls on the same context
-    // (ed25519_verify.c:282-286): the context has a device buffer of its own per calling thread and is uploaded only when
-    // its bytes differ from what the thread uploaded last (a 2080-byte memcmp against a synchronous ~12 us copy per call)
-    if (!t.vctx) C25519_TRY(hipMalloc(&t.vctx, 2080));
-    void* dctx = t.vctx;
-    if (!t.vctx_valid || memcmp(t.vctx_host, ctx, 2080) != 0) {
-        t.vctx_valid = false;
-        C25519_RC(c25519_host::upload_now(dctx, ctx, 2080));
-        memcpy(t.vctx_host, ctx, 2080);
-        t.vctx_valid = true;
-    }
+    void* dctx = nullptr;                                   // (one Verify_Init and MANY Verify_Check calls on the same context: a kept record)
+    C25519_RC(t.vctx.device_copy(&dctx, ctx));
+    const auto check_dev = rules == RULES_STRICT ? ed25519_Verify_Check_strict_dev : ed25519_Verify_Check_dev;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return (strict ? ed25519_Verify_Check_strict_dev : ed25519_Verify_Check_dev)(d[2], dctx, d[0], d[1], msg_size, c, st);
+                         return check_dev(d[2], dctx, d[0], d[1], msg_size, c, st);
                      });
 }
 
 int ed25519_Verify_Check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
                                size_t msg_size, size_t n)
 {
-    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, false);
+    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, RULES_PLAIN);
 }
 
 int ed25519_Verify_Check_strict_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
                                       size_t msg_size, size_t n)
 {
-    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, true);
-}
-
-// many contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
-// uploaded once per call into a grow-only device buffer of the calling thread (`buf`, `cap`: the verification contexts' or the signer
-// contexts'), the indices travel in pieces with the elements
-static int indexed_prepare(ThreadState& t, void*& buf, size_t& cap, size_t ctx_bytes, const void* ctxs, size_t n_ctx,
-                           const uint32_t* ctx_index, size_t n)
-{
-    if (n_ctx == 0) return bad_arg("no contexts");
-    if (n_ctx > ((size_t)1 << 32)) return bad_arg("more contexts than a uint32 index reaches");
-    for (size_t i = 0; i < n; i++)
-        if (ctx_index[i] >= n_ctx) return bad_arg("context index out of range");
-    C25519_RC(t.ensure());
-    const size_t bytes = n_ctx * ctx_bytes;
-    if (bytes > cap) {
-        if (buf) { C25519_TRY(hipMemset(buf, 0, cap)); C25519_TRY(hipFree(buf)); }
-        buf = nullptr;
-        cap = 0;
-        C25519_TRY(hipMalloc(&buf, bytes));
-        cap = bytes;
-    }
-    return c25519_host::upload_now(buf, ctxs, bytes);
+    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, RULES_STRICT);
 }
 
 int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
@@ -701,9 +616,8 @@ int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, t.vctxs, t.vctxs_cap, 2080, ctxs, n_ctx, ctx_index, n));
-    void* dctxs = t.vctxs;
+    void* dctxs = nullptr;
+    C25519_RC(indexed_prepare(&dctxs, tls().vctxs, 2080, ctxs, n_ctx, ctx_index, n));
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
@@ -717,22 +631,12 @@ int ed25519_Verify_Check_indexed_ragged_batch(int* verdict, const void* ctxs, si
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, t.vctxs, t.vctxs_cap, 2080, ctxs, n_ctx, ctx_index, n));
-    const int L = ThreadState::LANES - 1;
-    hipStream_t st = t.stream[L];
-    void *d_msgs, *d_off;
-    C25519_RC(ragged_upload(t, &d_msgs, &d_off, msgs, offsets, n));
-    C25519_RC(t.reserve_dev(L, 0, 64 * n));
-    C25519_RC(t.reserve_dev(L, 1, sizeof(uint32_t) * n));
-    C25519_RC(t.reserve_dev(L, 2, sizeof(int) * n));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], sig, 64 * n, hipMemcpyHostToDevice, st));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][1], ctx_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
-    C25519_RC(ed25519_Verify_Check_indexed_ragged_dev(t.dbuf[L][2], t.vctxs, n_ctx, t.dbuf[L][1], t.dbuf[L][0], d_msgs,
-                                                      (const uint64_t*)d_off, n, st));
-    C25519_TRY(hipMemcpyAsync(verdict, t.dbuf[L][2], sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    C25519_TRY(hipStreamSynchronize(st));
-    return 0;
+    void* dctxs = nullptr;
+    C25519_RC(indexed_prepare(&dctxs, tls().vctxs, 2080, ctxs, n_ctx, ctx_index, n));
+    return run_ragged(n, { Arr{ sig, nullptr, 64 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ nullptr, verdict, sizeof(int) } },
+                      msgs, offsets, [&](void** d, hipStream_t st) -> int {
+                          return ed25519_Verify_Check_indexed_ragged_dev(d[2], dctxs, n_ctx, d[1], d[0], d[3], (const uint64_t*)d[4], n, st);
+                      });
 }
 
 int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)
@@ -752,9 +656,8 @@ int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size
     C25519_API_CALL();
     if (!sig || !ctxs || !ctx_index || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, t.sctxs, t.sctxs_cap, 128, ctxs, n_ctx, ctx_index, n));
-    void* dctxs = t.sctxs;
+    void* dctxs = nullptr;
+    C25519_RC(indexed_prepare(&dctxs, tls().sctxs, 128, ctxs, n_ctx, ctx_index, n));
     return run_batch(n, { Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, sig, 64 } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
                          return ed25519_SignMessage_indexed_dev(d[2], dctxs, n_ctx, d[0], d[1], msg_size, c, st);
@@ -767,19 +670,12 @@ int ed25519_SignMessage_indexed_ragged_batch(unsigned char* sig, const void* ctx
     C25519_API_CALL();
     if (!sig || !ctxs || !ctx_index || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
-    ThreadState& t = tls();
-    C25519_RC(indexed_prepare(t, t.sctxs, t.sctxs_cap, 128, ctxs, n_ctx, ctx_index, n));
-    const int L = ThreadState::LANES - 1;
-    hipStream_t st = t.stream[L];
-    void *d_msgs, *d_off;
-    C25519_RC(ragged_upload(t, &d_msgs, &d_off, msgs, offsets, n));
-    C25519_RC(t.reserve_dev(L, 0, sizeof(uint32_t) * n));
-    C25519_RC(t.reserve_dev(L, 1, 64 * n));
-    C25519_TRY(hipMemcpyAsync(t.dbuf[L][0], ctx_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
-    C25519_RC(ed25519_SignMessage_indexed_ragged_dev(t.dbuf[L][1], t.sctxs, n_ctx, t.dbuf[L][0], d_msgs, (const uint64_t*)d_off, n, st));
-    C25519_TRY(hipMemcpyAsync(sig, t.dbuf[L][1], 64 * n, hipMemcpyDeviceToHost, st));
-    C25519_TRY(hipStreamSynchronize(st));
-    return 0;
+    void* dctxs = nullptr;
+    C25519_RC(indexed_prepare(&dctxs, tls().sctxs, 128, ctxs, n_ctx, ctx_index, n));
+    return run_ragged(n, { Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ nullptr, sig, 64 } }, msgs, offsets,
+                      [&](void** d, hipStream_t st) -> int {
+                          return ed25519_SignMessage_indexed_ragged_dev(d[1], dctxs, n_ctx, d[0], d[2], (const uint64_t*)d[3], n, st);
+                      });
 }
 
 void* ed25519_Verify_Init(void* context, const unsigned char* publicKey)

@@ -172,6 +172,7 @@ using c25519_host::ThreadState;
 using c25519_host::aligned16;
 using c25519_host::round_up;
 using c25519_host::run_batch;
+using c25519_host::run_ragged;
 using c25519_host::bad_arg;
 using c25519_host::tls;
 
@@ -186,6 +187,14 @@ int check_dev_args(size_t n, std::initializer_list<const void*> ptrs);
 // (engine_fixed_base.hip) blinding: null or a device-resident 192-byte context
 int keypair_dev(void* pub, void* priv, const void* sk, const void* blinding, size_t n, hipStream_t stream);
 int sign_dev(void* sig, const void* priv, const void* blinding, Msgs msgs, size_t n, hipStream_t stream);
+// (engine_verify.hip) RULES_STRICT runs the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh), RULES_ZIP215
+// the *_zip215 ones (cofactored equation, any point encoding, S < L) with their own kernel for the slow list
+enum VerifyRules { RULES_PLAIN, RULES_STRICT, RULES_ZIP215 };
+int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules);
+
+// the messages of a call: n of msg_size bytes each, or message i at msgs[offsets[i] .. offsets[i+1])
+inline Msgs fixed_msgs(const void* msg, size_t msg_size) { return Msgs{ (const uint8_t*)msg, msg_size, nullptr }; }
+inline Msgs ragged_msgs(const void* msgs, const void* offsets) { return Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }; }
 
 inline unsigned grid_for(size_t n, int block) { return (unsigned)((n + block - 1) / block); }
 // the wide comb is the default: sign 824 against 643 M/s, key pairs 1110 against 815 M/s at 2^20 (profiles/r05_ab_base_comb.txt)

@@ -615,7 +615,7 @@ int ed25519_SignMessage_dev(void* sig, const void* priv, const void* msg, size_t
 {
     C25519_API_CALL();
     if (!sig || !priv || (!msg && msg_size)) return bad_arg("null pointer");
-    return sign_dev(sig, priv, nullptr, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream);
+    return sign_dev(sig, priv, nullptr, fixed_msgs(msg, msg_size), n, (hipStream_t)stream);
 }
 
 int ed25519_SignMessage_blinded_dev(void* sig, const void* priv, const void* blinding, const void* msg, size_t msg_size,
@@ -623,7 +623,7 @@ int ed25519_SignMessage_blinded_dev(void* sig, const void* priv, const void* bli
 {
     C25519_API_CALL();
     if (!sig || !priv || !blinding || (!msg && msg_size)) return bad_arg("null pointer");
-    return sign_dev(sig, priv, blinding, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream);
+    return sign_dev(sig, priv, blinding, fixed_msgs(msg, msg_size), n, (hipStream_t)stream);
 }
 
 int ed25519_SignMessage_ragged_dev(void* sig, const void* priv, const void* msgs, const uint64_t* offsets, size_t n,
@@ -631,8 +631,7 @@ int ed25519_SignMessage_ragged_dev(void* sig, const void* priv, const void* msgs
 {
     C25519_API_CALL();
     if (!sig || !priv || !offsets) return bad_arg("null pointer");
-    return sign_dev(sig, priv, nullptr, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                    (hipStream_t)stream);
+    return sign_dev(sig, priv, nullptr, ragged_msgs(msgs, offsets), n, (hipStream_t)stream);
 }
 
 int ed25519_Sign_Init_dev(void* ctx, const void* priv, size_t n, void* stream)
@@ -707,7 +706,7 @@ int ed25519_SignMessage_indexed_dev(void* sig, const void* ctxs, size_t n_ctx, c
 {
     C25519_API_CALL();
     if (!sig || !ctxs || !ctx_index || (!msg && msg_size)) return bad_arg("null pointer");
-    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream);
+    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, fixed_msgs(msg, msg_size), n, (hipStream_t)stream);
 }
 
 int ed25519_SignMessage_indexed_ragged_dev(void* sig, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* msgs,
@@ -715,8 +714,7 @@ int ed25519_SignMessage_indexed_ragged_dev(void* sig, const void* ctxs, size_t n
 {
     C25519_API_CALL();
     if (!sig || !ctxs || !ctx_index || !offsets) return bad_arg("null pointer");
-    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                            (hipStream_t)stream);
+    return sign_indexed_dev(sig, ctxs, n_ctx, ctx_index, ragged_msgs(msgs, offsets), n, (hipStream_t)stream);
 }
 
 // one 192-byte blinding context from seed[0..seed_len) (device pointers)

@@ -839,9 +839,7 @@ thread_local LastVerify tl_last_verify;
 struct LastCheck { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
 thread_local LastCheck tl_last_check;
 
-// rules (fast only): RULES_STRICT runs the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh), RULES_ZIP215
-// the *_zip215 ones (cofactored equation, any point encoding, S < L) with their own kernel for the slow list
-enum VerifyRules { RULES_PLAIN, RULES_STRICT, RULES_ZIP215 };
+// rules (fast only): engine_common.cuh: VerifyRules
 template <typename MakeFin>
 int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin,
                VerifyRules rules = RULES_PLAIN)
@@ -920,12 +918,7 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
 
 }  // namespace
 
-extern "C" {
-
-size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return verify_scratch_bytes(n); }
-
-static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream,
-                      VerifyRules rules = RULES_PLAIN)
+int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules)
 {
     // tunable VERIFY_REFERENCE_ORDER = 1: every element through the reference-order kernels -- Verify_Init's 4-fold table per
     // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob).
@@ -937,6 +930,10 @@ static int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs,
                       [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules);
 }
 
+extern "C" {
+
+size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return verify_scratch_bytes(n); }
+
 // test hook: enc(T) instead of the verdict (what Verify_Check compares with enc(R)); device pointers
 int c25519_amd_verify_point_dev(void* out, const void* sig, const void* pk, const void* msg, size_t msg_size, size_t n,
                                 void* stream)
@@ -945,7 +942,7 @@ int c25519_amd_verify_point_dev(void* out, const void* sig, const void* pk, cons
     if (!out || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
     if (int rc = check_dev_args(n, { out, sig, pk })) return rc;
     if (n == 0) return 0;
-    return verify_run(sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, nullptr, false,
+    return verify_run(sig, pk, fixed_msgs(msg, msg_size), n, (hipStream_t)stream, nullptr, false,
                       [&](const ProjScratch& scr) { return FinishPack{ scr.a, scr.b, out, n, 1, 0, nullptr, 0, 0 }; });
 }
 
@@ -969,7 +966,7 @@ int ed25519_VerifySignature_dev(void* verdict, const void* sig, const void* pk, 
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream);
+    return verify_dev(verdict, sig, pk, fixed_msgs(msg, msg_size), n, (hipStream_t)stream, RULES_PLAIN);
 }
 
 int ed25519_VerifySignature_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
@@ -977,8 +974,7 @@ int ed25519_VerifySignature_ragged_dev(void* verdict, const void* sig, const voi
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                      (hipStream_t)stream);
+    return verify_dev(verdict, sig, pk, ragged_msgs(msgs, offsets), n, (hipStream_t)stream, RULES_PLAIN);
 }
 
 int ed25519_VerifySignature_strict_dev(void* verdict, const void* sig, const void* pk, const void* msg, size_t msg_size,
@@ -986,7 +982,7 @@ int ed25519_VerifySignature_strict_dev(void* verdict, const void* sig, const voi
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, RULES_STRICT);
+    return verify_dev(verdict, sig, pk, fixed_msgs(msg, msg_size), n, (hipStream_t)stream, RULES_STRICT);
 }
 
 int ed25519_VerifySignature_strict_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
@@ -994,8 +990,7 @@ int ed25519_VerifySignature_strict_ragged_dev(void* verdict, const void* sig, co
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                      (hipStream_t)stream, RULES_STRICT);
+    return verify_dev(verdict, sig, pk, ragged_msgs(msgs, offsets), n, (hipStream_t)stream, RULES_STRICT);
 }
 
 // the ZIP-215 verdict (include/curve25519_amd.h): same arguments, dispatch and tunables as ed25519_VerifySignature_dev
@@ -1004,7 +999,7 @@ int ed25519_VerifySignature_zip215_dev(void* verdict, const void* sig, const voi
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, (hipStream_t)stream, RULES_ZIP215);
+    return verify_dev(verdict, sig, pk, fixed_msgs(msg, msg_size), n, (hipStream_t)stream, RULES_ZIP215);
 }
 
 int ed25519_VerifySignature_zip215_ragged_dev(void* verdict, const void* sig, const void* pk, const void* msgs,
@@ -1012,8 +1007,7 @@ int ed25519_VerifySignature_zip215_ragged_dev(void* verdict, const void* sig, co
 {
     C25519_API_CALL();
     if (!verdict || !sig || !pk || !offsets) return bad_arg("null pointer");
-    return verify_dev(verdict, sig, pk, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets }, n,
-                      (hipStream_t)stream, RULES_ZIP215);
+    return verify_dev(verdict, sig, pk, ragged_msgs(msgs, offsets), n, (hipStream_t)stream, RULES_ZIP215);
 }
 
 // two-phase verification on the device: contexts are 2080-byte records (pk || 16 x 128-byte canonical rows),
@@ -1043,6 +1037,7 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
     if (n == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
+    const Msgs msgs = fixed_msgs(msg, msg_size);
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
     // a big batch under one key: both scalars over wide combs, if the context is Verify_Init's own and the key is on the
@@ -1058,8 +1053,7 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     tl_last_check = LastCheck();
     tl_last_check.ran = true;
     if (!try_wide && small) {                               // a few pairs: one per wave, the reference's order
-        k_ed25519_verify_check_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctx,
-                                                                    Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, tbl, take_done_word(n));
+        k_ed25519_verify_check_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctx, msgs, n, tbl, take_done_word(n));
         C25519_TRY(hipGetLastError());
         return 0;
     }
@@ -1095,14 +1089,14 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
         quads = one_key_quad_for(n);
         if (quads)                                          // four lanes per pair, the verdict in the same launch
             k_ed25519_verify_check_wide_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(
-                (int*)verdict, sig, (const u32*)ctx, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, wide_base, wide_key, wide_ok);
+                (int*)verdict, sig, (const u32*)ctx, msgs, n, wide_base, wide_key, wide_ok);
         else
             k_ed25519_verify_check_wide<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(
-                scr, sig, (const u32*)ctx, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, wide_base, wide_key, wide_ok);
+                scr, sig, (const u32*)ctx, msgs, n, wide_base, wide_key, wide_ok);
         C25519_TRY(hipGetLastError());
     }
     k_ed25519_verify_check_shared<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
-        scr, sig, (const u32*)ctx, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n, tbl, wide_ok);
+        scr, sig, (const u32*)ctx, msgs, n, tbl, wide_ok);
     C25519_TRY(hipGetLastError());
     // (the quad kernel has written the verdicts itself where the combs decided: the shared inversion then finds wide_ok set and leaves)
     C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
@@ -1165,8 +1159,7 @@ int ed25519_Verify_Check_indexed_dev(void* verdict, const void* ctxs, size_t n_c
 {
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
-    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, Msgs{ (const uint8_t*)msg, msg_size, nullptr }, n,
-                                    (hipStream_t)stream);
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, fixed_msgs(msg, msg_size), n, (hipStream_t)stream);
 }
 
 int ed25519_Verify_Check_indexed_ragged_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig,
@@ -1174,8 +1167,7 @@ int ed25519_Verify_Check_indexed_ragged_dev(void* verdict, const void* ctxs, siz
 {
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
-    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, Msgs{ (const uint8_t*)msgs, 0, (const unsigned long long*)offsets },
-                                    n, (hipStream_t)stream);
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, ragged_msgs(msgs, offsets), n, (hipStream_t)stream);
 }
 
 // test / accounting hook: did the calling thread's last ed25519_Verify_Check_* call on this device walk the two wide combs (1), or

@@ -517,4 +517,46 @@ int run_batch(size_t n, std::initializer_list<Arr> arrays, Launch launch, const 
     return failed;
 }
 
+// ---- ragged host calls: message i is msgs[offsets[i] .. offsets[i+1]), offsets has n + 1 entries (host memory) -----------
+// ONE piece on ONE stream: the arrays, the message bytes and the offsets are uploaded whole, `launch` gets the device pointers
+// in list order followed by the message bytes' and the offsets', the outputs come back and the call returns when the stream
+// has drained.  An error after the first copy was enqueued waits for the stream too: it may still be reading the caller's arrays.
+template <typename Launch>
+int run_ragged(size_t n, std::initializer_list<Arr> arrays, const unsigned char* msgs, const uint64_t* offsets, Launch launch)
+{
+    C25519_API_CALL();
+    ThreadState& t = tls();
+    C25519_RC(t.ensure());
+    // the download stream, idle between pipelined calls, and the buffer set that carries the same number (any set would do: no
+    // pipelined call of this thread is in flight)
+    constexpr int STREAM = ThreadState::LANES - 1, SET = STREAM;
+    constexpr int MSGS_SLOT = ThreadState::SLOTS - 2, OFFSETS_SLOT = ThreadState::SLOTS - 1;
+    hipStream_t st = t.stream[STREAM];
+    const Arr* arr = arrays.begin();
+    const int na = (int)arrays.size();
+    if (na > MSGS_SLOT) return bad_arg("internal: too many arrays");
+    const size_t msg_bytes = (size_t)offsets[n], off_bytes = sizeof(uint64_t) * (n + 1);
+    C25519_RC(t.reserve_dev(SET, MSGS_SLOT, msg_bytes));
+    C25519_RC(t.reserve_dev(SET, OFFSETS_SLOT, off_bytes));
+    for (int a = 0; a < na; a++) C25519_RC(t.reserve_dev(SET, a, arr[a].elem * n));
+    void* dptr[ThreadState::SLOTS] = {};
+    for (int a = 0; a < na; a++) dptr[a] = t.dbuf[SET][a];
+    dptr[na] = t.dbuf[SET][MSGS_SLOT];
+    dptr[na + 1] = t.dbuf[SET][OFFSETS_SLOT];
+    auto enqueue = [&]() -> int {
+        if (msg_bytes) C25519_TRY(hipMemcpyAsync(dptr[na], msgs, msg_bytes, hipMemcpyHostToDevice, st));
+        C25519_TRY(hipMemcpyAsync(dptr[na + 1], offsets, off_bytes, hipMemcpyHostToDevice, st));
+        for (int a = 0; a < na; a++)
+            if (arr[a].in) C25519_TRY(hipMemcpyAsync(dptr[a], arr[a].in, arr[a].elem * n, hipMemcpyHostToDevice, st));
+        C25519_RC(launch(dptr, st));
+        for (int a = 0; a < na; a++)
+            if (arr[a].out) C25519_TRY(hipMemcpyAsync(arr[a].out, dptr[a], arr[a].elem * n, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    const int rc = enqueue();
+    if (rc) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return rc; }
+    C25519_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 }  // namespace c25519_host
