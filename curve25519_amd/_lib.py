@@ -48,6 +48,13 @@ SIGNATURES = {
     "ed25519_VerifySignature_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_VerifySignature_zip215_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_zip215_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_VerifyBatch_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ed25519_VerifyBatch_zip215_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ed25519_VerifyBatch_zip215_batch": [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VerifyBatch_zip215_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "c25519_amd_verify_batch_last_equation": [],
+    "ed25519_VerifyBatch_scratch_bytes": [_sz],
+    "c25519_amd_verify_batch_point_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],
@@ -108,6 +115,8 @@ SIGNATURES = {
 }
 _RESTYPE = {
     "ed25519_VerifySignature_scratch_bytes": _sz,
+    "ed25519_VerifyBatch_scratch_bytes": _sz,
+    "c25519_amd_verify_batch_last_equation": C.c_long,
     "c25519_amd_verify_last_slow_elements": C.c_long,
     "c25519_amd_verify_check_last_wide": C.c_long,
     "c25519_amd_x25519_one_peer_last_wide": C.c_long,

@@ -239,6 +239,57 @@ def ed25519_VerifySignature_zip215_ragged(sig, pk, messages):
     return _verify_ragged(sig, pk, messages, "zip215")
 
 
+def _seed(seed):
+    """None, or 32 bytes as a ctypes buffer (it must outlive the call)"""
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    return C.create_string_buffer(seed, 32)
+
+
+def ed25519_VerifyBatch_zip215(sig, pk, msg, seed=None, verdicts=False):
+    """ZIP-215 batch verification, one random linear combination per call (include/curve25519_amd.h): 1 if every signature is valid,
+    0 otherwise (wrongly 1 with probability at most 2^-128 over the seed).  seed: 32 fresh, unpredictable bytes, or None for
+    getrandom(2).  verdicts=True returns (all_valid, int32[n]): all ones, or ed25519_VerifySignature_zip215's verdicts when the batch
+    fails."""
+    sig = _np(sig, 64, "sig")
+    pk = _np(pk, 32, "pk")
+    n = sig.shape[0]
+    if pk.shape[0] != n:
+        raise ValueError("sig and pk must have the same number of rows")
+    msg, msg_size = _msgs(msg, n)
+    ok = C.c_int(-1)
+    verdict = np.empty(n, np.int32) if verdicts else None
+    sd = _seed(seed)
+    _lib.check(_lib.load().ed25519_VerifyBatch_zip215_batch(C.byref(ok), _ptr(verdict) if verdicts else None, _ptr(sig), _ptr(pk),
+                                                            _ptr(msg), msg_size, n, sd), "ed25519_VerifyBatch_zip215_batch")
+    return (ok.value, verdict) if verdicts else ok.value
+
+
+def ed25519_VerifyBatch_zip215_ragged(sig, pk, messages, seed=None, verdicts=False):
+    """ed25519_VerifyBatch_zip215 with per-element message lengths (`messages`: sequence of bytes-like)."""
+    sig = _np(sig, 64, "sig")
+    pk = _np(pk, 32, "pk")
+    n = sig.shape[0]
+    if len(messages) != n or pk.shape[0] != n:
+        raise ValueError("one message and one key per signature")
+    flat, offsets = _ragged(messages)
+    ok = C.c_int(-1)
+    verdict = np.empty(n, np.int32) if verdicts else None
+    sd = _seed(seed)
+    _lib.check(_lib.load().ed25519_VerifyBatch_zip215_ragged_batch(C.byref(ok), _ptr(verdict) if verdicts else None, _ptr(sig), _ptr(pk),
+                                                                   _ptr(flat), _ptr(offsets), n, sd),
+               "ed25519_VerifyBatch_zip215_ragged_batch")
+    return (ok.value, verdict) if verdicts else ok.value
+
+
+def verify_batch_last_equation():
+    """1: the calling thread's last ed25519_VerifyBatch_zip215 call ran the equation, 0: the per-element path, -1: no such call"""
+    return int(_lib.load().c25519_amd_verify_batch_last_equation())
+
+
 def ed25519_Verify_Init(pk):
     """n x ed25519_Verify_Init: per-key contexts, uint8[n, 2080] (pk || 16 rows x 4 canonical elements)."""
     pk = _np(pk, 32, "pk")
@@ -462,6 +513,35 @@ def ed25519_VerifySignature_strict_dev(verdict, sig, pk, msg):
 def ed25519_VerifySignature_zip215_dev(verdict, sig, pk, msg):
     """Device form of ed25519_VerifySignature_zip215: verdict int32[n, 1]."""
     _verify_dev(verdict, sig, pk, msg, "zip215")
+
+
+def ed25519_VerifyBatch_zip215_dev(result, sig, pk, msg, seed):
+    """Device form of ed25519_VerifyBatch_zip215: result int32[1, 1]; seed: 32 bytes of HOST memory (required); does not synchronise."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(result, 1, "result", 1, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(pk, 32, "pk", n, device=d),
+            _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_VerifyBatch_zip215_dev(*args, msg.shape[1], n, _seed(seed), st), "ed25519_VerifyBatch_zip215_dev")
+
+
+def ed25519_VerifyBatch_zip215_ragged_dev(result, sig, pk, flat, offsets, seed):
+    """Device form with ragged messages: flat uint8[total, 1] message bytes, offsets int64[n + 1, 1] (read as uint64)."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(result, 1, "result", 1, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(pk, 32, "pk", n, device=d),
+            _check(flat, 1, "flat", device=d), _check(offsets, 1, "offsets", n + 1, dtype=torch.int64, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_VerifyBatch_zip215_ragged_dev(*args, n, _seed(seed), st), "ed25519_VerifyBatch_zip215_ragged_dev")
+
+
+def verify_batch_point_dev(out, sig, pk, msg, seed):
+    """Test hook (c25519_amd_verify_batch_point_dev): out uint8[1, 32] <- enc(T) of the batch equation's point, always by the
+    equation's kernels."""
+    n, d = sig.shape[0], sig.device
+    args = (_check(out, 32, "out", 1, device=d), _check(sig, 64, "sig"), _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().c25519_amd_verify_batch_point_dev(*args, msg.shape[1], n, _seed(seed), st), "c25519_amd_verify_batch_point_dev")
 
 
 def ed25519_Verify_Check_strict_dev(verdict, ctx, sig, msg):

@@ -6,7 +6,7 @@
                                             #    tools/cycle_probe.py and bench.py; never loaded by the product)
 
 The .so is git-ignored but travels with gpurun snapshots; it is rebuilt when any source under
-csrc/ or include/ is newer.  The engine's four translation units (csrc/engine_*.hip) and csrc/multi_device.hip are compiled
+csrc/ or include/ is newer.  The engine's translation units (csrc/engine_*.hip) and csrc/multi_device.hip are compiled
 side by side into curve25519_amd/_obj/ and linked.
 """
 import os
@@ -35,7 +35,7 @@ def is_stale() -> bool:
     return any(os.path.getmtime(s) > t for s in _sources())
 
 
-ENGINE_UNITS = ("engine_x25519", "engine_fixed_base", "engine_verify", "engine_api")     # csrc/engine_common.cuh says which is which
+ENGINE_UNITS = ("engine_x25519", "engine_fixed_base", "engine_verify", "engine_batch_eq", "engine_api")     # csrc/engine_common.cuh says which is which
 OBJ = os.path.join(PKG, "_obj")             # git-ignored, does not travel: the GPU box gets the linked libraries
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-pragma-unroll-threshold=131072"]
 # -pragma-unroll-threshold: k_batch_invert keeps 16 elements and their prefix products in registers, which needs its
@@ -50,7 +50,7 @@ def _hipcc() -> str:
 
 
 def _compile(units, force=False, verbose=False):
-    """units: [(source stem, object name, extra flags)]; the stale ones are compiled side by side (the engine's four translation
+    """units: [(source stem, object name, extra flags)]; the stale ones are compiled side by side (the engine's translation
     units take 9-40 s each: ~40 s for all of them instead of 100 s as one), each into a file of its own that is renamed when
     complete (several ranks of one node may find the library stale at the same time)."""
     os.makedirs(OBJ, exist_ok=True)

@@ -96,6 +96,8 @@ enum Tunable {
     T_QUAD_MAX,                 //   QUAD_MAX = 0: never; unset: per operation (engine.hip)
     T_ONE_PEER_WIDE,            // curve25519_dh_CreateSharedKey_one_peer: smallest batch that builds a wide comb for a NEW peer key (0: never)
     T_PEER_INDEXED_MIN,         // curve25519_dh_CreateSharedKey_indexed: smallest batch that walks the contexts' rows (0: always)
+    T_BATCH_EQ_MIN,             // ed25519_VerifyBatch_zip215: smallest call that runs the batch equation (0: never; 1: always)
+    T_BATCH_EQ_WINDOW,          // ... and its window width, 7..13 (anything else: the built-in choice by n)
     T_COUNT
 };
 constexpr long T_UNSET = -1;
@@ -103,7 +105,7 @@ inline const char* const* tunable_names()
 {
     static const char* const names[T_COUNT] = { "COOP_MAX", "XF_SPLIT", "INV_K", "VERIFY_REFERENCE_ORDER", "MULTI_FORCE_GATHER",
                                                 "MULTI_VIRTUAL", "BASE_COMB", "HELPER_THREADS", "VERIFY_LAT_CAP_BITS", "ONE_KEY_WIDE", "LADDER2_MAX",
-                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN" };
+                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN", "BATCH_EQ_MIN", "BATCH_EQ_WINDOW" };
     return names;
 }
 inline std::atomic<long>* tunable_table()

@@ -2,12 +2,13 @@
 // between the kernels of a pass, the completion word, the shared inversion (k_batch_invert, its output encoders, launch_invert)
 // and the host-side helpers of the *_dev entry points (tables, argument checks, launch policy).
 //
-// The engine is FOUR translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
+// The engine is FIVE translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
 //   engine_x25519.hip      the Montgomery-ladder kernels; curve25519_dh_CreateSharedKey / _CalculatePublicKey (*_dev)
 //   engine_fixed_base.hip  the constant tables; key pairs, signatures, CalculatePublicKey_fast, blinding contexts (*_dev)
 //   engine_verify.hip      verification: lattice path, reference order, two-phase / one key (*_dev)
+//   engine_batch_eq.hip    ZIP-215 batch verification: one equation per call, a bucket-method multi-scalar multiplication (*_dev, *_batch)
 //   engine_api.hip         library state, unit-test hooks, the host-pointer *_batch forms, the reference's single-call prototypes
-// engine.hip includes all four as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
+// engine.hip includes all five as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
 // compile (the same kernels).  Entry points are declared in include/curve25519_amd.h, include/curve25519_dh.h and
 // include/ed25519_signature.h (each cites the reference prototype it replaces).
 //
@@ -190,7 +191,9 @@ int sign_dev(void* sig, const void* priv, const void* blinding, Msgs msgs, size_
 // (engine_verify.hip) RULES_STRICT runs the *_strict twins of the lattice path's kernels (input rules of strict25519.cuh), RULES_ZIP215
 // the *_zip215 ones (cofactored equation, any point encoding, S < L) with their own kernel for the slow list
 enum VerifyRules { RULES_PLAIN, RULES_STRICT, RULES_ZIP215 };
-int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules);
+// last_in_call = false: more kernels of the same call follow (the AND of ed25519_VerifyBatch_zip215_*), so a call of ONE element's
+// completion word is not this call's to signal
+int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules, bool last_in_call = true);
 
 // the messages of a call: n of msg_size bytes each, or message i at msgs[offsets[i] .. offsets[i+1])
 inline Msgs fixed_msgs(const void* msg, size_t msg_size) { return Msgs{ (const uint8_t*)msg, msg_size, nullptr }; }

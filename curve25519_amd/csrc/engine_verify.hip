@@ -842,7 +842,7 @@ thread_local LastCheck tl_last_check;
 // rules (fast only): engine_common.cuh: VerifyRules
 template <typename MakeFin>
 int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin,
-               VerifyRules rules = RULES_PLAIN)
+               VerifyRules rules = RULES_PLAIN, bool last_in_call = true)
 {
     const bool strict = rules == RULES_STRICT, zip215 = rules == RULES_ZIP215;
     const u32* tbl = nullptr;
@@ -900,7 +900,7 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
             C25519_TRY(hipGetLastError());
         }
         (zip215 ? k_ed25519_verify_slow_zip215 : k_ed25519_verify_slow)<<<grid, ED_BLOCK, 0, stream>>>(fs, verdict, sig, pk, msgs, tbl,
-                                                                                                     take_done_word(n));
+                                                                                                     last_in_call ? take_done_word(n) : DoneWord{ nullptr, 0 });
         C25519_TRY(hipGetLastError());
         tl_last_verify.count = report; tl_last_verify.stream = stream;
         tl_last_verify.generation = tls().generation;       // the report word and the stream die with the thread's slabs
@@ -918,7 +918,8 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
 
 }  // namespace
 
-int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules)
+int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules,
+                              bool last_in_call)
 {
     // tunable VERIFY_REFERENCE_ORDER = 1: every element through the reference-order kernels -- Verify_Init's 4-fold table per
     // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob).
@@ -927,7 +928,7 @@ int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Ms
     if (int rc = check_dev_args(n, { verdict, sig, pk })) return rc;
     if (n == 0) return 0;
     return verify_run(sig, pk, msgs, n, stream, (int*)verdict, fast,
-                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules);
+                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules, last_in_call);
 }
 
 extern "C" {

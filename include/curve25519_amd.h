@@ -53,7 +53,7 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * of more than 3584 elements with the peer the calling thread's last comb was built for walks that comb whatever its size;
  * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
- * 0 = always walk).
+ * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW (ed25519_VerifyBatch_zip215_*, see there).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -303,6 +303,59 @@ int ed25519_VerifySignature_zip215_ragged_batch(int *verdict, const unsigned cha
 int ed25519_VerifySignature_zip215_ragged_dev(void *verdict, const void *sig, const void *pk, const void *msgs,
                                               const uint64_t *offsets, size_t n, void *stream);
 
+/* ZIP-215 BATCH verification: ONE equation per call (ed25519-zebra's batch::Verifier, ed25519-consensus).  For n triples and a
+ * 32-byte seed, with z_i = the first 16 bytes of SHA-512(seed || le64(i)) read little-endian (i = the element's index in the call, also
+ * for a host call that is cut into pieces), k_i = SHA-512(sig_i[0..31] || pk_i || msg_i) mod L and A_i, R_i decoded as the ZIP-215 calls
+ * above decode them, `result` is 1 exactly when
+ *   1. every element has S_i < L, a key that decodes and an R that decodes (rules 1-3 above), and
+ *   2. [8]([sum z_i S_i mod L]B - sum [z_i]R_i - sum [z_i k_i mod L]A_i) is the neutral element.
+ * COMPLETENESS IS EXACT: if every element's ed25519_VerifySignature_zip215_* verdict is 1, result is 1 for every seed (the sum of
+ * points that [8] maps to the neutral element is mapped there too).  SOUNDNESS IS PROBABILISTIC: if any verdict is 0, result is 0
+ * except with probability at most 2^-128 over a uniform seed (after [8], a bad element's defect lies in the prime-order group, the
+ * z_i are 128-bit and 2^128 < L, so at most one value of its z_i cancels whatever the others sum to).  THE SEED MUST BE FRESH AND
+ * UNPREDICTABLE to whoever produced the signatures: someone who knows it before choosing them can make invalid ones cancel.  Never
+ * reuse one, never derive it from the batch.  A batch equation under the plain or strict rules would not be sound; there is none.
+ * n == 0: result 1.  The *_dev forms never synchronise; their seed is HOST memory, read before the call returns (it travels in kernel
+ * arguments); a null seed is an argument error there.  result: one int in device memory, 16-byte aligned like every device pointer.
+ * The *_batch forms run the same through the host pipeline -- a call cut into pieces runs one equation per piece and ANDs the results
+ * -- and a null seed means 32 bytes from getrandom(2).  verdict (NULL or n ints): all ones when the result is 1; when it is 0 the call
+ * runs ed25519_VerifySignature_zip215_batch on the same inputs and returns its verdicts (the fallback every consumer of a batch
+ * verifier writes by hand).  With verdict == NULL only *all_valid is written.
+ * Device path (csrc/engine_batch_eq.hip, DESIGN.md "ZIP-215 batch equation"): a bucket-method multi-scalar multiplication over the 2n
+ * decoded points -- signed c-bit digits, a counting sort of (point, sign) by (window, bucket), one lane per bucket, running sums per
+ * window -- plus one walk of the wide base comb.  Tunables: BATCH_EQ_MIN, the smallest n (of a call, or of a piece of a host call) that
+ * runs the equation; smaller ones run ed25519_VerifySignature_zip215_dev into scratch and AND the verdicts (0 = never the equation,
+ * 1 = always); BATCH_EQ_WINDOW, c = 7..13 (anything else: the built-in choice by n).
+ * Measured on MI355X, honest inputs, device-resident (profiles/verify_batch_rate.txt; per-element path / best equation, ms):
+ * 2^16 0.82 / 1.67, 2^17 1.45 / 1.98, 2^18 2.74 / 2.74, 2^19 5.11 / 4.16, 2^20 9.77 / 7.17 (1.36 x; 146 M signatures/s).  Hence BATCH_EQ_MIN defaults to
+ * 2^19 = 524288, the smallest measured size from which the equation wins by more than the rounds' spread (2^18 is a tie), and the
+ * built-in width is c = 10 below 2^16 elements and c = 13 from there (the fastest measured one; c = 8 ties at 2^10).  Below that the
+ * equation is a chain of eight launches with a sequential tail of 0.94 ms, against 0.3-2.7 ms for the whole per-element pass.
+ * WHAT A HOST CALL GETS with the default tunables: the pipeline cuts a *_batch call into pieces of n / 8 rows (not below 2^16), and
+ * each piece decides for itself, so only a call of 2^22 elements or more runs the equation; a smaller one runs the per-element kernels
+ * plus the AND -- the same result, the same verdict fallback, at ed25519_VerifySignature_zip215_batch's rate.  Ragged host calls are one
+ * piece and run the equation from 2^19.  A caller with 2^19 .. 2^22 elements who wants the equation uses the *_dev form (or lowers
+ * BATCH_EQ_MIN).  One call takes at most 2^26 elements (the equation's index entries are addressed with 32 bits): a larger n is an
+ * argument error of every form and of the hook. */
+int ed25519_VerifyBatch_zip215_dev(void *result, const void *sig, const void *pk, const void *msg, size_t msg_size, size_t n,
+                                   const unsigned char *seed, void *stream);
+int ed25519_VerifyBatch_zip215_ragged_dev(void *result, const void *sig, const void *pk, const void *msgs, const uint64_t *offsets,
+                                          size_t n, const unsigned char *seed, void *stream);
+int ed25519_VerifyBatch_zip215_batch(int *all_valid, int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                     const unsigned char *msg, size_t msg_size, size_t n, const unsigned char *seed);
+int ed25519_VerifyBatch_zip215_ragged_batch(int *all_valid, int *verdict, const unsigned char *sig, const unsigned char *pk,
+                                            const unsigned char *msgs, const uint64_t *offsets, size_t n, const unsigned char *seed);
+/* did the calling thread's last ed25519_VerifyBatch_zip215_* call (the last piece of a host call) run the equation (1) or the
+ * per-element path (0)?  -1: no such call. */
+long c25519_amd_verify_batch_last_equation(void);
+/* bytes of device scratch the equation takes for n elements at the width c it would run with (BATCH_EQ_WINDOW or the built-in choice),
+ * wa = ceil(255 / c) windows for a key's scalar, wz = ceil(130 / c) for an R's, K = (wa + 1) * 2^(c-1) buckets (the R's top window has
+ * buckets of its own), r4 = rounded up to 4:
+ *   4 * (2n * 40 + (K + wa + 1) * 40 + n * (wa + wz) + 16 * ceil(n / 256) + r4(n) + 2 K + 4)
+ * -- per element two packed 128-byte rows, two biased scalars and wa + wz index entries: 444 bytes at c = 13, 520 at c = 8; per bucket
+ * 168 bytes (14.5 MB at c = 13). */
+size_t ed25519_VerifyBatch_scratch_bytes(size_t n);
+
 /* ed25519_VerifySignature_* decide every element whose key decompresses onto the curve with an exact
  * lattice-shortened walk (csrc/verify_fast.cuh, ~134 doublings instead of 255) and run the reference's own operation
  * order only for the others (set C25519_AMD_VERIFY_REFERENCE_ORDER=1 to force it for everything).  This reports how many
@@ -399,6 +452,11 @@ int c25519_amd_base_table(unsigned char *out /* 24576 bytes */);
  * (reference source/ed25519_verify.c:309-310) instead of the verdict; device pointers, out is n x 32 bytes */
 int c25519_amd_verify_point_dev(void *out, const void *sig, const void *pk, const void *msg, size_t msg_size,
                                 size_t n, void *stream);
+/* test hook: enc(T) of the point inside [8](...) of ed25519_VerifyBatch_zip215_*, always by the equation's kernels, for any n >= 1;
+ * elements with S >= L or a key or R that does not decode are left out of the sums.  The role of c25519_amd_verify_point_dev.
+ * out: 32 bytes of device memory. */
+int c25519_amd_verify_batch_point_dev(void *out, const void *sig, const void *pk, const void *msg, size_t msg_size, size_t n,
+                                      const unsigned char *seed, void *stream);
 
 /* device field arithmetic on n pairs of 32-byte little-endian values taken mod p = 2^255-19 (host pointers):
  * out[i] = canonical(op(a[i], b[i])), op 0 mul, 1 square, 2 add, 3 sub, 4 inverse, 5 a^((p-5)/8),

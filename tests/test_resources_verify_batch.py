@@ -1,0 +1,40 @@
+"""Register / scratch budgets of the ZIP-215 batch equation's kernels (csrc/engine_batch_eq.hip), from the compiler's own remarks
+(tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
+import os
+import shutil
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+KERNELS = ["points", "scalars", "count", "scan", "scatter", "buckets", "windows", "tail", "and"]
+
+
+@pytest.fixture(scope="module")
+def usage():
+    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
+        pytest.skip("hipcc not available")
+    import resource_usage
+    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
+
+
+def test_the_equation_has_its_kernels_and_none_is_a_zip215_twin(usage):
+    """tests/test_resources_verify_zip215.py asserts the exact set of kernels whose name contains zip215: these must stay out of it"""
+    mine = sorted(k for k in usage if "batcheq" in k)
+    assert mine == sorted("k_ed25519_batcheq_" + n for n in KERNELS)
+    assert not any("zip215" in k for k in mine)
+
+
+@pytest.mark.parametrize("name", KERNELS)
+def test_kernel_is_spill_free(usage, name):
+    k = usage["k_ed25519_batcheq_" + name]
+    assert k.get("scratch", 0) == 0 and k.get("vgpr_spill", 0) == 0 and k.get("sgpr_spill", 0) == 0, k
+
+
+def test_the_per_point_and_per_bucket_kernels_keep_four_waves_per_simd(usage):
+    """decoding (one square root per lane) and the bucket sums are the stages every point passes through: 128 registers or fewer"""
+    for name in ("points", "scalars", "buckets"):
+        k = usage["k_ed25519_batcheq_" + name]
+        assert k["vgpr"] + k.get("agpr", 0) <= 128, k
