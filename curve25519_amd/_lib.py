@@ -55,6 +55,12 @@ SIGNATURES = {
     "c25519_amd_verify_batch_last_equation": [],
     "ed25519_VerifyBatch_scratch_bytes": [_sz],
     "c25519_amd_verify_batch_point_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ed25519_VerifyBatch_zip215_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ed25519_VerifyBatch_zip215_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ed25519_VerifyBatch_zip215_indexed_batch": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VerifyBatch_zip215_indexed_ragged_batch": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_VerifyBatch_indexed_scratch_bytes": [_sz, _sz],
+    "c25519_amd_verify_batch_indexed_point_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],
@@ -116,6 +122,7 @@ SIGNATURES = {
 _RESTYPE = {
     "ed25519_VerifySignature_scratch_bytes": _sz,
     "ed25519_VerifyBatch_scratch_bytes": _sz,
+    "ed25519_VerifyBatch_indexed_scratch_bytes": _sz,
     "c25519_amd_verify_batch_last_equation": C.c_long,
     "c25519_amd_verify_last_slow_elements": C.c_long,
     "c25519_amd_verify_check_last_wide": C.c_long,

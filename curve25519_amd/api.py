@@ -286,7 +286,8 @@ def ed25519_VerifyBatch_zip215_ragged(sig, pk, messages, seed=None, verdicts=Fal
 
 
 def verify_batch_last_equation():
-    """1: the calling thread's last ed25519_VerifyBatch_zip215 call ran the equation, 0: the per-element path, -1: no such call"""
+    """1: the calling thread's last ed25519_VerifyBatch_zip215 call (indexed or not) ran the equation, 0: the per-element path, -1: no
+    such call"""
     return int(_lib.load().c25519_amd_verify_batch_last_equation())
 
 
@@ -351,6 +352,41 @@ def ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages):
                                                                       _ptr(flat), _ptr(offsets), n),
                "ed25519_Verify_Check_indexed_ragged_batch")
     return ok
+
+
+def ed25519_VerifyBatch_zip215_indexed(keys, idx, sig, msg, seed=None, verdicts=False):
+    """ed25519_VerifyBatch_zip215 with coalesced keys: uint8[n_key, 32] raw keys, uint32[n] indices, element i verified under
+    keys[idx[i]]; the terms of one key are merged into one point of the equation (include/curve25519_amd.h).  The result, and the
+    verdicts of verdicts=True, are ed25519_VerifyBatch_zip215's on keys[idx].  An index >= n_key raises EngineError."""
+    sig = _np(sig, 64, "sig")
+    n = sig.shape[0]
+    keys, idx = _ctx_index(keys, idx, n, 32)
+    msg, msg_size = _msgs(msg, n)
+    ok = C.c_int(-1)
+    verdict = np.empty(n, np.int32) if verdicts else None
+    sd = _seed(seed)
+    _lib.check(_lib.load().ed25519_VerifyBatch_zip215_indexed_batch(C.byref(ok), _ptr(verdict) if verdicts else None, _ptr(keys),
+                                                                    keys.shape[0], _ptr(idx), _ptr(sig), _ptr(msg), msg_size, n, sd),
+               "ed25519_VerifyBatch_zip215_indexed_batch")
+    return (ok.value, verdict) if verdicts else ok.value
+
+
+def ed25519_VerifyBatch_zip215_indexed_ragged(keys, idx, sig, messages, seed=None, verdicts=False):
+    """ed25519_VerifyBatch_zip215_indexed with per-element message lengths (`messages`: sequence of bytes-like)."""
+    sig = _np(sig, 64, "sig")
+    n = sig.shape[0]
+    keys, idx = _ctx_index(keys, idx, n, 32)
+    if len(messages) != n:
+        raise ValueError("one message per signature")
+    flat, offsets = _ragged(messages)
+    ok = C.c_int(-1)
+    verdict = np.empty(n, np.int32) if verdicts else None
+    sd = _seed(seed)
+    _lib.check(_lib.load().ed25519_VerifyBatch_zip215_indexed_ragged_batch(C.byref(ok), _ptr(verdict) if verdicts else None, _ptr(keys),
+                                                                           keys.shape[0], _ptr(idx), _ptr(sig), _ptr(flat),
+                                                                           _ptr(offsets), n, sd),
+               "ed25519_VerifyBatch_zip215_indexed_ragged_batch")
+    return (ok.value, verdict) if verdicts else ok.value
 
 
 def base_folding8_table():
@@ -542,6 +578,42 @@ def verify_batch_point_dev(out, sig, pk, msg, seed):
     args = (_check(out, 32, "out", 1, device=d), _check(sig, 64, "sig"), _check(pk, 32, "pk", n, device=d), _check(msg, None, "msg", n, device=d))
     with _on(sig) as st:
         _lib.check(_lib.load().c25519_amd_verify_batch_point_dev(*args, msg.shape[1], n, _seed(seed), st), "c25519_amd_verify_batch_point_dev")
+
+
+def ed25519_VerifyBatch_zip215_indexed_dev(result, keys, idx, sig, msg, seed):
+    """Device form of ed25519_VerifyBatch_zip215_indexed: keys uint8[n_key, 32], idx int32[n, 1] (read as uint32), result int32[1, 1];
+    seed: 32 bytes of HOST memory (required).  An index >= n_key gives result 0 (nothing is checked on the host); does not synchronise."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(result, 1, "result", 1, dtype=torch.int32, device=d), _check(keys, 32, "keys", device=d), keys.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_VerifyBatch_zip215_indexed_dev(*args, msg.shape[1], n, _seed(seed), st),
+                   "ed25519_VerifyBatch_zip215_indexed_dev")
+
+
+def ed25519_VerifyBatch_zip215_indexed_ragged_dev(result, keys, idx, sig, flat, offsets, seed):
+    """Device form with ragged messages: flat uint8[total, 1] message bytes, offsets int64[n + 1, 1] (read as uint64)."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(result, 1, "result", 1, dtype=torch.int32, device=d), _check(keys, 32, "keys", device=d), keys.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(flat, 1, "flat", device=d),
+            _check(offsets, 1, "offsets", n + 1, dtype=torch.int64, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_VerifyBatch_zip215_indexed_ragged_dev(*args, n, _seed(seed), st),
+                   "ed25519_VerifyBatch_zip215_indexed_ragged_dev")
+
+
+def verify_batch_indexed_point_dev(out, keys, idx, sig, msg, seed):
+    """Test hook (c25519_amd_verify_batch_indexed_point_dev): out uint8[1, 32] <- enc(T) of the COALESCED equation's point, always by the
+    equation's kernels."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(out, 32, "out", 1, device=d), _check(keys, 32, "keys", device=d), keys.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(msg, None, "msg", n, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().c25519_amd_verify_batch_indexed_point_dev(*args, msg.shape[1], n, _seed(seed), st),
+                   "c25519_amd_verify_batch_indexed_point_dev")
 
 
 def ed25519_Verify_Check_strict_dev(verdict, ctx, sig, msg):

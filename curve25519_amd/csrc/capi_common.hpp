@@ -98,6 +98,7 @@ enum Tunable {
     T_PEER_INDEXED_MIN,         // curve25519_dh_CreateSharedKey_indexed: smallest batch that walks the contexts' rows (0: always)
     T_BATCH_EQ_MIN,             // ed25519_VerifyBatch_zip215: smallest call that runs the batch equation (0: never; 1: always)
     T_BATCH_EQ_WINDOW,          // ... and its window width, 7..13 (anything else: the built-in choice by n)
+    T_BATCH_EQ_INDEXED_MIN,     // ed25519_VerifyBatch_zip215_indexed: smallest call that runs the coalesced equation (0: never; 1: always)
     T_COUNT
 };
 constexpr long T_UNSET = -1;
@@ -105,7 +106,8 @@ inline const char* const* tunable_names()
 {
     static const char* const names[T_COUNT] = { "COOP_MAX", "XF_SPLIT", "INV_K", "VERIFY_REFERENCE_ORDER", "MULTI_FORCE_GATHER",
                                                 "MULTI_VIRTUAL", "BASE_COMB", "HELPER_THREADS", "VERIFY_LAT_CAP_BITS", "ONE_KEY_WIDE", "LADDER2_MAX",
-                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN", "BATCH_EQ_MIN", "BATCH_EQ_WINDOW" };
+                                                "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN", "BATCH_EQ_MIN", "BATCH_EQ_WINDOW",
+                                                "BATCH_EQ_INDEXED_MIN" };
     return names;
 }
 inline std::atomic<long>* tunable_table()
@@ -289,11 +291,11 @@ struct ThreadState {
     size_t dcap[SETS][SLOTS] = {};
     // this thread's copies of what its last calls were given (KeptRecord, GrowArray above): the 2080-byte context of
     // ed25519_Verify_Check_*batch, the 192-byte blinding context, the one-peer call's key; the n_ctx x 2080 / 1600 / 128 bytes of the
-    // indexed verification, X25519 and signing calls (the last are secret)
+    // indexed verification, X25519 and signing calls (the last are secret); the n_key x 32 key bytes of the indexed batch equation
     KeptRecord<2080> vctx;
     KeptRecord<192> bctx;
     KeptRecord<32> peer;
-    GrowArray vctxs, pctxs, sctxs;
+    GrowArray vctxs, pctxs, sctxs, bkeys;
     void* hbuf[SETS][SLOTS] = {};          // pinned host staging (hipHostMalloc)
     size_t hcap[SETS][SLOTS] = {};
     // The completion word of a call of ONE element (host_pipeline.hpp: zero-copy calls): pinned host memory the call's last
@@ -512,7 +514,7 @@ struct ThreadState {
         if (done_word) { (void)hipHostFree(done_word); done_word = nullptr; }
         done_offered = done_taken = false;
         vctx.release(); bctx.release(); peer.release();
-        vctxs.release(); pctxs.release(); sctxs.release();
+        vctxs.release(); pctxs.release(); sctxs.release(); bkeys.release();
         for (int l = 0; l < LANES; l++) {
             free_slab(lane_work[l]);
             if (stream[l]) (void)hipStreamDestroy(stream[l]);

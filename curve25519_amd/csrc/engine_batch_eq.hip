@@ -82,18 +82,21 @@ __global__ void __launch_bounds__(BE_BLOCK) k_ed25519_batcheq_scalars(BatchEqScr
 // stage 3, twice: blockIdx.y = window, blockIdx.x = a run of `pts` points.  The workgroup counts its points' digits per bucket in LDS,
 // then touches each global counter it needs ONCE: to add its count (count pass), or to reserve that many slots of the bucket's list
 // (scatter pass), which its lanes then fill in whatever order the LDS atomics hand out.
+// Points 0 .. nk - 1 are keys, nk .. N - 1 the R's; the flag of R point p is flags[p - rflag] (rflag = n where key i and R i share
+// element i's flag, 0 where every point has a flag of its own: the coalesced equation).
 template <bool Scatter>
-C25519_DEV void batcheq_digits(const BatchEqScratch& s, size_t n, unsigned pts, const BatchEqShape& shape, u32* hist, u32* base)
+C25519_DEV void batcheq_digits(const BatchEqScratch& s, size_t nk, size_t N, size_t rflag, unsigned pts, const BatchEqShape& shape, u32* hist,
+                               u32* base)
 {
     const int w = blockIdx.y;
-    const size_t N = 2 * n, p0 = (size_t)blockIdx.x * pts, p1 = p0 + pts < N ? p0 + pts : N;
-    if (p0 >= n ? msm_window_digit(shape, w, true) < 0 : (p1 <= n && w == shape.wa)) return;   // (uniform) no point of this run has a digit here
+    const size_t p0 = (size_t)blockIdx.x * pts, p1 = p0 + pts < N ? p0 + pts : N;
+    if (p0 >= nk ? msm_window_digit(shape, w, true) < 0 : (p1 <= nk && w == shape.wa)) return;   // (uniform) no point of this run has a digit here
     for (int b = threadIdx.x; b < shape.buckets; b += BE_BLOCK) hist[b] = 0;
     __syncthreads();
     auto digit_of = [&](size_t p) -> int {
-        const bool is_r = p >= n;
+        const bool is_r = p >= nk;
         const int dw = msm_window_digit(shape, w, is_r);
-        if (dw < 0 || s.flags[is_r ? p - n : p]) return 0;
+        if (dw < 0 || s.flags[is_r ? p - rflag : p]) return 0;
         return msm_digit(s.sc + p, N, dw, shape.c, is_r ? shape.wz : shape.wa);
     };
     for (size_t p = p0 + threadIdx.x; p < p1; p += BE_BLOCK) {
@@ -121,13 +124,13 @@ C25519_DEV void batcheq_digits(const BatchEqScratch& s, size_t n, unsigned pts, 
 __global__ void __launch_bounds__(BE_BLOCK) k_ed25519_batcheq_count(BatchEqScratch s, size_t n, unsigned pts, BatchEqShape shape)
 {
     __shared__ u32 hist[BE_MAX_BUCKETS];
-    batcheq_digits<false>(s, n, pts, shape, hist, nullptr);
+    batcheq_digits<false>(s, n, 2 * n, n, pts, shape, hist, nullptr);
 }
 
 __global__ void __launch_bounds__(BE_BLOCK) k_ed25519_batcheq_scatter(BatchEqScratch s, size_t n, unsigned pts, BatchEqShape shape)
 {
     __shared__ u32 hist[BE_MAX_BUCKETS], base[BE_MAX_BUCKETS];
-    batcheq_digits<true>(s, n, pts, shape, hist, base);
+    batcheq_digits<true>(s, n, 2 * n, n, pts, shape, hist, base);
 }
 
 // exclusive scan of the K counts into cursor: one workgroup, a run of counters per lane
@@ -252,6 +255,136 @@ __global__ void __launch_bounds__(BE_AND_BLOCK) k_ed25519_batcheq_and(int* resul
     if (!ok) atomicOr(&state[0], 1u);
     __threadfence();
     if (atomicAdd(&state[1], 1u) == gridDim.x - 1) *result = atomicOr(&state[0], 0u) ? 0 : 1;
+}
+
+// ---- the coalesced equation (ed25519_VerifyBatch_zip215_indexed_*): n elements name K keys, N = K + n points (the keys, then the R's).
+// BatchEqScratch carved for that shape (keyeq_carve): flags has one word per POINT -- a key's: it does not decode, or its scalar is
+// zero; an R's: its element is left out --, and keysum holds eight 64-bit sums per key.  The scan, the buckets, the windows and the
+// tail are the kernels above.
+
+// stages 1 and 2: one lane per point.  A key that does not decode only gets its flag: whether that matters is up to who names it.
+__global__ void __launch_bounds__(ED_BLOCK, 3) k_ed25519_keyeq_points(BatchEqScratch s, const void* sig, const void* keys, size_t K, size_t n)
+{
+    const size_t j = (size_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (j >= K + n) return;
+    const bool is_r = j >= K;
+    u32 w[8], row[24];
+    if (is_r) load32(w, sig, 2 * (j - K)); else load32(w, keys, j);
+    const u32 ok = msm_point_row(row, w);
+    uint4* out = reinterpret_cast<uint4*>(s.rows + j * MSM_ROW_WORDS);
+#pragma unroll
+    for (int g = 0; g < 6; g++) out[g] = make_uint4(row[4 * g], row[4 * g + 1], row[4 * g + 2], row[4 * g + 3]);
+    if (!ok) {
+        s.flags[j] = 1u;
+        if (is_r) atomicOr(s.reject, 1u);
+    }
+}
+
+// stage 3: one lane per element.  The s_i leave as in k_ed25519_batcheq_scalars.  The a_i of the elements that stay are summed per key,
+// word by word, in LDS first -- an open-addressed table of the keys this workgroup met, twice as many slots as lanes -- and each slot
+// in use then adds its eight sums to the key's in memory: one 64-bit atomic per workgroup, key and word, none of which returns a value.
+constexpr int KE_SLOTS = 2 * BE_BLOCK;
+constexpr u32 KE_EMPTY = 0xffffffffu;                        // (a key index is below 2^26)
+__global__ void __launch_bounds__(BE_BLOCK) k_ed25519_keyeq_scalars(BatchEqScratch s, unsigned long long* keysum, const void* sig, const void* keys,
+                                                                    const u32* key_index, Msgs msgs, size_t n, size_t K, BatchEqSeed seed,
+                                                                    unsigned long long index0, BatchEqShape shape)
+{
+    __shared__ u32 part[16];
+    __shared__ u32 slot_key[KE_SLOTS];
+    __shared__ unsigned long long slot_sum[KE_SLOTS][8];
+    if (threadIdx.x < 16) part[threadIdx.x] = 0;
+    for (int t = threadIdx.x; t < KE_SLOTS; t += BE_BLOCK) {
+        slot_key[t] = KE_EMPTY;
+#pragma unroll
+        for (int j = 0; j < 8; j++) slot_sum[t][j] = 0;
+    }
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * BE_BLOCK + threadIdx.x;
+    u32 sv[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (i < n) {
+        u32 pkw[8], Rw[8], Sw[8], a[8], z[8];
+        const u32 idx = key_index[i];
+        const bool in_range = idx < K;
+        load32(pkw, keys, in_range ? idx : 0);               // (nothing outside keys is read)
+        load32(Rw, sig, 2 * i);
+        load32(Sw, sig, 2 * i + 1);
+        const u32 s_ok = msm_scalars_canonical(a, z, sv, pkw, Rw, Sw, msgs.ptr(i), msgs.len(i), seed.w, index0 + i, shape.c);
+        soa_store8(s.sc, K + n, K + i, z);
+        if (!s_ok || !in_range || s.flags[K + i] || s.flags[idx]) {
+            s.flags[K + i] = 1u;
+            atomicOr(s.reject, 1u);
+#pragma unroll
+            for (int j = 0; j < 8; j++) sv[j] = 0;
+        } else {
+            u32 h = (idx * 0x9e3779b1u) >> 23;               // 9 bits: KE_SLOTS
+            for (;;) {
+                const u32 prev = atomicCAS(&slot_key[h], KE_EMPTY, idx);
+                if (prev == KE_EMPTY || prev == idx) break;
+                h = (h + 1) & (KE_SLOTS - 1);
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) atomicAdd(&slot_sum[h][j], (unsigned long long)a[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        u32 v = (sv[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&part[j], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) s.partial[(size_t)blockIdx.x * 16 + threadIdx.x] = part[threadIdx.x];
+    for (int t = threadIdx.x; t < KE_SLOTS; t += BE_BLOCK) {
+        const u32 key = slot_key[t];
+        if (key == KE_EMPTY) continue;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const unsigned long long v = slot_sum[t][j];
+            if (v) atomicAdd(&keysum[(size_t)key * 8 + j], v);
+        }
+    }
+}
+static_assert(KE_SLOTS == 512, "k_ed25519_keyeq_scalars hashes a key index to 9 bits");
+
+// stage 4: one lane per key: its sums -> its one biased scalar, at the key's point
+__global__ void __launch_bounds__(BE_BLOCK) k_ed25519_keyeq_fold(BatchEqScratch s, const unsigned long long* keysum, size_t K, size_t n, BatchEqShape shape)
+{
+    const size_t j = (size_t)blockIdx.x * BE_BLOCK + threadIdx.x;
+    if (j >= K) return;
+    u64 sum[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) sum[w] = keysum[j * 8 + w];
+    u32 a[8];
+    const u32 any = msm_key_fold(a, sum, shape.c);
+    soa_store8(s.sc, K + n, j, a);
+    if (!any) s.flags[j] = 1u;
+}
+
+// stage 5: the digit passes with the key / R boundary at K
+__global__ void __launch_bounds__(BE_BLOCK) k_ed25519_keyeq_count(BatchEqScratch s, size_t K, size_t n, unsigned pts, BatchEqShape shape)
+{
+    __shared__ u32 hist[BE_MAX_BUCKETS];
+    batcheq_digits<false>(s, K, K + n, 0, pts, shape, hist, nullptr);
+}
+
+__global__ void __launch_bounds__(BE_BLOCK) k_ed25519_keyeq_scatter(BatchEqScratch s, size_t K, size_t n, unsigned pts, BatchEqShape shape)
+{
+    __shared__ u32 hist[BE_MAX_BUCKETS], base[BE_MAX_BUCKETS];
+    batcheq_digits<true>(s, K, K + n, 0, pts, shape, hist, base);
+}
+
+// calls below BATCH_EQ_INDEXED_MIN: pk[i] = keys[key_index[i]] for the per-element kernels; an index out of range takes key 0 and
+// sets the AND's finding (state[0] of k_ed25519_batcheq_and) itself
+__global__ void __launch_bounds__(BE_BLOCK) k_ed25519_keyeq_gather(void* pk, const void* keys, const u32* key_index, size_t n, size_t K, u32* state)
+{
+    const size_t i = (size_t)blockIdx.x * BE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 idx = key_index[i];
+    u32 w[8];
+    load32(w, keys, idx < K ? idx : 0);
+    store32(pk, i, w);
+    if (idx >= K) atomicOr(&state[0], 1u);
 }
 
 namespace {
@@ -395,6 +528,133 @@ int batcheq_fresh_seed(unsigned char (&seed)[32])
     return 0;
 }
 
+// ---- the coalesced equation: host side ----
+// Measured on MI355X (tools/verify_batch_indexed_rate.py, profiles/verify_batch_indexed_rate.txt; K <= 65536 keys; per-element call on
+// the gathered keys / un-indexed equation / this one, ms): 2^17 1.45-1.48 / 1.95-2.05 / 1.94-2.00, 2^18 2.70-2.75 / 2.70-2.78 / 2.46-2.53,
+// 2^19 5.12-5.17 / 4.06-4.16 / 3.38-3.51, 2^20 9.66-9.79 / 7.05-7.22 / 5.51-5.59 -- this one wins from 2^18 by more than the rounds' spread
+// at every such K.  K = n (nothing merges) costs 0.25-0.27 ms over the un-indexed equation at 2^19 and 2^20 and wins from 2^19 only.  The
+// faster width is the un-indexed call's in every cell (batcheq_width).
+constexpr long BATCH_EQ_INDEXED_MIN_DEFAULT = 1L << 18;
+inline bool keyeq_for(size_t n)
+{
+    const long mn = c25519_host::tunable_or(c25519_host::T_BATCH_EQ_INDEXED_MIN, BATCH_EQ_INDEXED_MIN_DEFAULT);
+    return mn > 0 && n >= (size_t)mn;
+}
+
+// words of the coalesced equation's scratch (the formula of include/curve25519_amd.h)
+inline size_t keyeq_words(size_t n, size_t K, const BatchEqShape& sh)
+{
+    const size_t KB = (size_t)(sh.wa + 1) * sh.buckets, N = K + n;
+    return N * (MSM_ROW_WORDS + 8) + (KB + sh.wa + 1) * MSM_EXT_WORDS + n * sh.wz + K * sh.wa + 16 * batcheq_blocks(n) + 16 * K + round_up(N, 4) + 2 * KB + 4;
+}
+
+struct KeyEqScratch { BatchEqScratch s; unsigned long long* keysum; size_t zeroed_words; };
+inline KeyEqScratch keyeq_carve(u32* base, size_t n, size_t K, const BatchEqShape& sh)
+{
+    const size_t KB = (size_t)(sh.wa + 1) * sh.buckets, N = K + n;
+    KeyEqScratch k;
+    BatchEqScratch& s = k.s;
+    s.rows = base;
+    s.buckets = s.rows + N * MSM_ROW_WORDS;
+    s.windows = s.buckets + KB * MSM_EXT_WORDS;
+    s.sc = s.windows + (size_t)(sh.wa + 1) * MSM_EXT_WORDS;
+    s.partial = s.sc + 8 * N;
+    u32* sums = s.partial + 16 * batcheq_blocks(n);          // (an even number of words from the slab's start: 64-bit sums)
+    k.keysum = reinterpret_cast<unsigned long long*>(sums);
+    s.flags = sums + 16 * K;                                 // keysum, flags, counts, cursor, reject: one run, zeroed by one fill
+    s.counts = s.flags + round_up(N, 4);
+    s.cursor = s.counts + KB;
+    s.reject = s.cursor + KB;
+    s.entries = s.reject + 4;
+    k.zeroed_words = 16 * K + round_up(N, 4) + 2 * KB + 4;
+    return k;
+}
+
+// the coalesced equation for n >= 1 elements over K >= 1 keys; result: one int, or point_out: enc(T)
+int keyeq_equation(int* result, void* point_out, const void* keys, size_t K, const void* key_index, const void* sig, Msgs msgs, size_t n,
+                   const BatchEqSeed& seed, unsigned long long index0, hipStream_t stream)
+{
+    const u32* wide = nullptr;
+    C25519_RC(wide_tables(&wide));
+    const BatchEqShape sh = batcheq_shape(n);
+    const unsigned KB = (unsigned)((sh.wa + 1) * sh.buckets);
+    const size_t N = K + n;
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, keyeq_words(n, K, sh) * sizeof(u32), stream));
+    const KeyEqScratch k = keyeq_carve((u32*)w, n, K, sh);
+    const BatchEqScratch& s = k.s;
+    C25519_TRY(hipMemsetAsync(k.keysum, 0, k.zeroed_words * sizeof(u32), stream));
+    k_ed25519_keyeq_points<<<grid_for(N, ED_BLOCK), ED_BLOCK, 0, stream>>>(s, sig, keys, K, n);
+    C25519_TRY(hipGetLastError());
+    const unsigned blocks = (unsigned)batcheq_blocks(n);
+    k_ed25519_keyeq_scalars<<<blocks, BE_BLOCK, 0, stream>>>(s, k.keysum, sig, keys, (const u32*)key_index, msgs, n, K, seed, index0, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_keyeq_fold<<<grid_for(K, BE_BLOCK), BE_BLOCK, 0, stream>>>(s, k.keysum, K, n, sh);
+    C25519_TRY(hipGetLastError());
+    const unsigned pts = std::max(BE_BLOCK, 2 * sh.buckets);                      // (as batcheq_equation)
+    const dim3 dgrid(grid_for(N, (int)pts), (unsigned)sh.wa + 1);
+    k_ed25519_keyeq_count<<<dgrid, BE_BLOCK, 0, stream>>>(s, K, n, pts, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_scan<<<1, BE_SCAN_BLOCK, 0, stream>>>(s, KB);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_keyeq_scatter<<<dgrid, BE_BLOCK, 0, stream>>>(s, K, n, pts, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_buckets<<<grid_for(KB, ED_BLOCK), ED_BLOCK, 0, stream>>>(s, KB);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_windows<<<(unsigned)sh.wa + 1, 64, 0, stream>>>(s, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_tail<<<1, 128, 0, stream>>>(s, sh, blocks, wide, result, point_out);
+    C25519_TRY(hipGetLastError());
+    return lease.release();
+}
+
+// below BATCH_EQ_INDEXED_MIN: the keys gathered behind batcheq_per_element's layout, then that path
+int keyeq_per_element(int* result, const void* keys, size_t K, const void* key_index, const void* sig, Msgs msgs, size_t n, hipStream_t stream)
+{
+    const size_t inner = round_up(ed25519_VerifySignature_scratch_bytes(n), 256);
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, inner + round_up(n, 4) * sizeof(int) + 16 + n * 32, stream));
+    int* verdict = (int*)((char*)w + inner);
+    u32* state = (u32*)(verdict + round_up(n, 4));
+    void* pk = state + 4;
+    C25519_TRY(hipMemsetAsync(state, 0, 2 * sizeof(u32), stream));
+    k_ed25519_keyeq_gather<<<grid_for(n, BE_BLOCK), BE_BLOCK, 0, stream>>>(pk, keys, (const u32*)key_index, n, K, state);
+    C25519_TRY(hipGetLastError());
+    C25519_RC(verify_dev(verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false));
+    k_ed25519_batcheq_and<<<std::min(grid_for(n, BE_AND_BLOCK), 256u), BE_AND_BLOCK, 0, stream>>>(result, verdict, n, state);
+    C25519_TRY(hipGetLastError());
+    return lease.release();
+}
+
+int keyeq_check_counts(size_t n, size_t n_key)
+{
+    if (n > BATCH_EQ_MAX_N) return bad_arg("batch too large for one call (n > 2^26)");
+    if (n_key > BATCH_EQ_MAX_N) return bad_arg("too many keys for one call (n_key > 2^26)");
+    if (n && !n_key) return bad_arg("no keys");
+    return 0;
+}
+
+int keyeq_dev(void* result, const void* keys, size_t n_key, const void* key_index, const void* sig, Msgs msgs, size_t n,
+              const unsigned char* seed, unsigned long long index0, hipStream_t stream, bool result_is_ours = false)
+{
+    if (!seed) return bad_arg("null seed");
+    C25519_RC(keyeq_check_counts(n, n_key));
+    if (int rc = check_dev_args(n, { result_is_ours ? nullptr : result, keys, key_index, sig })) return rc;
+    if (n == 0) {                                            // the empty AND
+        k_ed25519_batcheq_and<<<1, BE_AND_BLOCK, 0, stream>>>((int*)result, nullptr, 0, nullptr);
+        C25519_TRY(hipGetLastError());
+        return 0;
+    }
+    const bool eq = keyeq_for(n);
+    tl_batch_last_equation = eq ? 1 : 0;
+    if (!eq) return keyeq_per_element((int*)result, keys, n_key, key_index, sig, msgs, n, stream);
+    BatchEqSeed sd;
+    memcpy(sd.w, seed, 32);
+    return keyeq_equation((int*)result, nullptr, keys, n_key, key_index, sig, msgs, n, sd, index0, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -508,6 +768,110 @@ int ed25519_VerifyBatch_zip215_ragged_batch(int* all_valid, int* verdict, const 
                          }));
     if (!batcheq_finish(all_valid, verdict, 1, n) && verdict)
         return ed25519_VerifySignature_zip215_ragged_batch(verdict, sig, pk, msgs, offsets, n);
+    return 0;
+}
+
+// ---- the coalesced forms: keys[key_index[i]] is element i's key ----
+
+size_t ed25519_VerifyBatch_indexed_scratch_bytes(size_t n, size_t n_key) { return keyeq_words(n, n_key, batcheq_shape(n)) * sizeof(u32); }
+
+int ed25519_VerifyBatch_zip215_indexed_dev(void* result, const void* keys, size_t n_key, const void* key_index, const void* sig,
+                                           const void* msg, size_t msg_size, size_t n, const unsigned char* seed, void* stream)
+{
+    C25519_API_CALL();
+    if (!result || !keys || !key_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    return keyeq_dev(result, keys, n_key, key_index, sig, fixed_msgs(msg, msg_size), n, seed, 0, (hipStream_t)stream);
+}
+
+int ed25519_VerifyBatch_zip215_indexed_ragged_dev(void* result, const void* keys, size_t n_key, const void* key_index, const void* sig,
+                                                  const void* msgs, const uint64_t* offsets, size_t n, const unsigned char* seed, void* stream)
+{
+    C25519_API_CALL();
+    if (!result || !keys || !key_index || !sig || !offsets) return bad_arg("null pointer");
+    return keyeq_dev(result, keys, n_key, key_index, sig, ragged_msgs(msgs, offsets), n, seed, 0, (hipStream_t)stream);
+}
+
+// test hook: enc(T) of the COALESCED point, always by the equation's kernels; device pointers
+int c25519_amd_verify_batch_indexed_point_dev(void* out, const void* keys, size_t n_key, const void* key_index, const void* sig,
+                                              const void* msg, size_t msg_size, size_t n, const unsigned char* seed, void* stream)
+{
+    C25519_API_CALL();
+    if (!out || !keys || !key_index || !sig || (!msg && msg_size) || !seed) return bad_arg("null pointer");
+    if (n == 0) return bad_arg("the hook takes n >= 1");
+    C25519_RC(keyeq_check_counts(n, n_key));
+    if (int rc = check_dev_args(n, { out, keys, key_index, sig })) return rc;
+    BatchEqSeed sd;
+    memcpy(sd.w, seed, 32);
+    return keyeq_equation(nullptr, out, keys, n_key, key_index, sig, fixed_msgs(msg, msg_size), n, sd, 0, (hipStream_t)stream);
+}
+
+namespace {
+// what a host form does before any work: the counts, every index, then the keys' upload into the calling thread's kept array
+int keyeq_prepare(void** dkeys, const unsigned char* keys, size_t n_key, const uint32_t* key_index, size_t n)
+{
+    C25519_RC(keyeq_check_counts(n, n_key));
+    for (size_t i = 0; i < n; i++)
+        if (key_index[i] >= n_key) return bad_arg("key index out of range");
+    C25519_RC(tls().ensure());
+    return tls().bkeys.upload(dkeys, keys, n_key * 32);
+}
+
+// the verdicts of a failed batch: ed25519_VerifySignature_zip215_*batch on the gathered keys
+std::vector<unsigned char> keyeq_gathered(const unsigned char* keys, const uint32_t* key_index, size_t n)
+{
+    std::vector<unsigned char> pk(n * 32);
+    for (size_t i = 0; i < n; i++) memcpy(&pk[32 * i], keys + 32 * (size_t)key_index[i], 32);
+    return pk;
+}
+}  // namespace
+
+int ed25519_VerifyBatch_zip215_indexed_batch(int* all_valid, int* verdict, const unsigned char* keys, size_t n_key, const uint32_t* key_index,
+                                             const unsigned char* sig, const unsigned char* msg, size_t msg_size, size_t n,
+                                             const unsigned char* seed)
+{
+    C25519_API_CALL();
+    if (!all_valid || !keys || !key_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    if (n == 0) { *all_valid = 1; return 0; }
+    void* dkeys = nullptr;
+    C25519_RC(keyeq_prepare(&dkeys, keys, n_key, key_index, n));
+    *all_valid = 1;
+    unsigned char fresh[32];
+    if (!seed) { C25519_RC(batcheq_fresh_seed(fresh)); seed = fresh; }
+    const size_t chunk = c25519_host::piece_rows(n, 64 + sizeof(uint32_t) + msg_size);    // (run_batch's own cut of these three arrays)
+    C25519_RC(tl_piece_results.reserve((n + chunk - 1) / chunk));
+    size_t pieces = 0;
+    C25519_RC(run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ key_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size } },
+                        [&](void** d, size_t c, size_t lo, hipStream_t st) -> int {
+                            if (pieces >= tl_piece_results.cap) return bad_arg("internal: more pieces than result words");
+                            int* word = tl_piece_results.word + pieces++;
+                            *word = 0;
+                            return keyeq_dev(word, dkeys, n_key, d[1], d[0], fixed_msgs(d[2], msg_size), c, seed, lo, st, true);
+                        }));
+    if (!batcheq_finish(all_valid, verdict, pieces, n) && verdict)
+        return ed25519_VerifySignature_zip215_batch(verdict, sig, keyeq_gathered(keys, key_index, n).data(), msg, msg_size, n);
+    return 0;
+}
+
+int ed25519_VerifyBatch_zip215_indexed_ragged_batch(int* all_valid, int* verdict, const unsigned char* keys, size_t n_key,
+                                                    const uint32_t* key_index, const unsigned char* sig, const unsigned char* msgs,
+                                                    const uint64_t* offsets, size_t n, const unsigned char* seed)
+{
+    C25519_API_CALL();
+    if (!all_valid || !keys || !key_index || !sig || !offsets) return bad_arg("null pointer");
+    if (n == 0) { *all_valid = 1; return 0; }
+    void* dkeys = nullptr;
+    C25519_RC(keyeq_prepare(&dkeys, keys, n_key, key_index, n));
+    *all_valid = 1;
+    unsigned char fresh[32];
+    if (!seed) { C25519_RC(batcheq_fresh_seed(fresh)); seed = fresh; }
+    C25519_RC(tl_piece_results.reserve(1));
+    tl_piece_results.word[0] = 0;
+    C25519_RC(run_ragged(n, { Arr{ sig, nullptr, 64 }, Arr{ key_index, nullptr, sizeof(uint32_t) } }, msgs, offsets,
+                         [&](void** d, hipStream_t st) -> int {
+                             return keyeq_dev(tl_piece_results.word, dkeys, n_key, d[1], d[0], ragged_msgs(d[2], d[3]), n, seed, 0, st, true);
+                         }));
+    if (!batcheq_finish(all_valid, verdict, 1, n) && verdict)
+        return ed25519_VerifySignature_zip215_ragged_batch(verdict, sig, keyeq_gathered(keys, key_index, n).data(), msgs, offsets, n);
     return 0;
 }
 

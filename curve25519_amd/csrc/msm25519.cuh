@@ -12,6 +12,9 @@
 //   buckets   one lane per (window, bucket): the sum of the rows its list names (ge_add_pa; a negative digit flips the row)
 //   windows   sum_d d * Bucket_d by running sums over a chunk of buckets, chunks joined by a short multiply with the chunk's offset
 //   tail      Horner over the windows, + [s] B, then the hook's encoding or three doublings and the neutral test
+// The coalesced form (ed25519_VerifyBatch_zip215_indexed_*: n elements over K keys, N = K + n points) sums the canonical a_i of a key's
+// elements first (msm_scalars_canonical, integer sums per 32-bit word, msm_key_fold) and gives the key ONE scalar; every later stage is
+// the same code over fewer points.
 // The kernels add the cross-lane parts (counting sort with atomics, reductions); the CPU emulator (tests/host_emul/verify_batch.cpp)
 // drives the same functions with a host counting sort in between.  The a = -1 unified additions are complete on the curve, so equal
 // points, P + (-P) and the small-order points of the conformance grid take the same code as everything else.
@@ -100,9 +103,9 @@ C25519_DEV void msm_challenge(u32 (&z)[8], const u32 (&seedw)[8], u64 index)
     for (int j = 0; j < 8; j++) z[j] = j < 4 ? le[j] : 0u;
 }
 
-// stage 1 for one element: a = z k mod L and z, both BIASED for width c; s = z S mod L (canonical).  Returns all-ones iff S < L.
-C25519_DEV u32 msm_scalars(u32 (&a)[8], u32 (&z)[8], u32 (&s)[8], const u32 (&pkw)[8], const u32 (&Rw)[8], const u32 (&Sw)[8],
-                           const uint8_t* msg, size_t len, const u32 (&seedw)[8], u64 index, int c)
+// the scalars of one element: a = z k mod L and s = z S mod L, both CANONICAL, and z BIASED for width c.  Returns all-ones iff S < L.
+C25519_DEV u32 msm_scalars_canonical(u32 (&a)[8], u32 (&z)[8], u32 (&s)[8], const u32 (&pkw)[8], const u32 (&Rw)[8], const u32 (&Sw)[8],
+                                     const uint8_t* msg, size_t len, const u32 (&seedw)[8], u64 index, int c)
 {
     u32 k[8];
     ed_hram(k, Rw, pkw, msg, len);
@@ -112,9 +115,39 @@ C25519_DEV u32 msm_scalars(u32 (&a)[8], u32 (&z)[8], u32 (&s)[8], const u32 (&pk
     sc_mod(a);
     sc_mul(s, z, Sw);
     sc_mod(s);
-    msm_bias(a, c, msm_windows_a(c));
     msm_bias(z, c, msm_windows_z(c));
     return zip215_pair_flags(Sw) ? 0u : 0xffffffffu;
+}
+
+// stage 1 for one element: a = z k mod L and z, both BIASED for width c; s = z S mod L (canonical).  Returns all-ones iff S < L.
+C25519_DEV u32 msm_scalars(u32 (&a)[8], u32 (&z)[8], u32 (&s)[8], const u32 (&pkw)[8], const u32 (&Rw)[8], const u32 (&Sw)[8],
+                           const uint8_t* msg, size_t len, const u32 (&seedw)[8], u64 index, int c)
+{
+    const u32 ok = msm_scalars_canonical(a, z, s, pkw, Rw, Sw, msg, len, seedw, index, c);
+    msm_bias(a, c, msm_windows_a(c));
+    return ok;
+}
+
+// the coalesced equation (ed25519_VerifyBatch_zip215_indexed_*), one key: the eight 64-bit sums of its elements' a_i, word by word
+// (each sum below 2^58: at most 2^26 elements), -> their total mod L, BIASED for width c.  Returns all-ones iff the total is not zero
+// (a key with total zero has no digits: nobody named it, or only rejected elements did, or its terms cancel).
+C25519_DEV u32 msm_key_fold(u32 (&a)[8], const u64 (&sum)[8], int c)
+{
+    u32 t[16];
+    u64 carry = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        carry += j < 8 ? sum[j] : 0ull;
+        t[j] = (u32)carry;
+        carry >>= 32;
+    }
+    sc_reduce512(a, t);
+    sc_mod(a);
+    u32 any = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) any |= a[j];
+    msm_bias(a, c, msm_windows_a(c));
+    return any ? 0xffffffffu : 0u;
 }
 
 // stage 2 for one point: the packed row of -P.  Returns all-ones iff the string decodes.

@@ -53,7 +53,7 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * of more than 3584 elements with the peer the calling thread's last comb was built for walks that comb whatever its size;
  * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
- * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW (ed25519_VerifyBatch_zip215_*, see there).
+ * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -356,6 +356,62 @@ long c25519_amd_verify_batch_last_equation(void);
  * 168 bytes (14.5 MB at c = 13). */
 size_t ed25519_VerifyBatch_scratch_bytes(size_t n);
 
+/* ed25519_VerifyBatch_zip215_* with COALESCED KEYS (what ed25519-zebra's and ed25519-consensus's batch verifiers do for their main
+ * workload, many signatures from a small, known key set): keys is n_key x 32 raw key bytes (no context record: the equation builds no
+ * tables), key_index is n x uint32, and element i's key is pk_i = keys[key_index[i]].  With z_i as above and
+ * k_i = SHA-512(sig_i[0..31] || pk_i || msg_i) mod L, `result` is 1 exactly when
+ *   1. every element has S_i < L, an R that decodes and a key pk_i that decodes, and
+ *   2. [8]([sum z_i S_i mod L]B - sum_i [z_i]R_i - sum_j [(sum over i with key_index[i] = j of z_i k_i) mod L]A_j) is the neutral element
+ * -- the terms under one key are merged, so the sum runs over K = n_key points instead of n, and every key is decoded once.
+ * FOR EVERY INPUT AND SEED `result` EQUALS what ed25519_VerifyBatch_zip215_* gives on the gathered keys pk_i with that seed, and
+ * completeness, soundness and the seed rule read as above.  The POINT inside [8](...) may differ from the un-coalesced one by an
+ * 8-torsion point when a key has mixed order, because [a mod L]A != [a]A there; [8] removes the difference (the hook below returns the
+ * coalesced point).  A key that no element names is not part of the batch: it does not affect the result, even if it does not
+ * decode.  The same 32 bytes at two indices are two points.  n == 0: result 1.  A null pointer, n_key == 0 with n > 0, n > 2^26 or
+ * n_key > 2^26 is an argument error.
+ *   *_dev never synchronises, takes its seed from HOST memory as above and cannot check the indices: an index >= n_key rejects its
+ *   element (result 0), and nothing outside keys is read.
+ *   *_batch checks every index on the host: one >= n_key refuses the call before any work, all_valid and verdict untouched.  It
+ *   uploads keys once per call into a device buffer of the calling thread (zeroed before it is freed by c25519_amd_thread_release() or
+ *   a larger call) and runs sig, key_index and msg through the host pipeline, one equation per piece, the element index counting
+ *   through the call; a null seed means getrandom(2).  verdict as above: when the result is 0 the call gathers the keys on the host
+ *   and returns ed25519_VerifySignature_zip215_batch's verdicts.
+ * Device path (csrc/engine_batch_eq.hip, DESIGN.md "Coalesced keys"): the points are the K keys, then the n R's; the canonical
+ * a_i = z_i k_i mod L of a key's elements are added up as eight 32-bit words into eight 64-bit sums (below 2^58 with n <= 2^26;
+ * integer addition: the result does not depend on the order) -- in LDS per workgroup first, then one no-return 64-bit atomic per
+ * workgroup, distinct key and word --, one lane per key folds them mod L, and the digit passes, buckets, windows and tail are the
+ * equation's own over N = K + n points.  Tunables: BATCH_EQ_INDEXED_MIN, with BATCH_EQ_MIN's semantics (0 = never the equation,
+ * 1 = always); below it a call gathers the keys into scratch and runs ed25519_VerifySignature_zip215_dev plus the AND (an index out
+ * of range still gives 0).  BATCH_EQ_WINDOW applies unchanged; the built-in width is chosen by n as above.
+ * c25519_amd_verify_batch_last_equation() reports these calls too.
+ * Measured on MI355X, honest inputs, device-resident, n elements over K <= 65536 keys (profiles/verify_batch_indexed_rate.txt;
+ * per-element call on the gathered keys / un-indexed equation / this call, ms): 2^17 1.45-1.48 / 1.95-2.05 / 1.94-2.00,
+ * 2^18 2.70-2.75 / 2.70-2.78 / 2.46-2.53, 2^19 5.12-5.17 / 4.06-4.16 / 3.38-3.51, 2^20 9.66-9.79 / 7.05-7.22 / 5.51-5.59 (1.26-1.30 x the
+ * un-indexed equation, 1.73-1.78 x the per-element call; 190 M signatures/s).  Hence BATCH_EQ_INDEXED_MIN defaults to 2^18 = 262144,
+ * the smallest measured size from which this call beats the per-element one by more than the rounds' spread at every measured
+ * K <= 65536, and the built-in width stays the un-indexed call's (the faster one in every measured cell).  K = n -- every element
+ * its own key, nothing to merge -- is the price of the accumulation: +0.25 ms over the un-indexed equation at 2^20 (7.45 against 7.21
+ * ms), +0.27 at 2^19, within the spread below; such a call wins over the per-element one from 2^19 only (2^18: 2.84 against 2.71 ms).
+ * What a host call gets: as above, a *_batch call is cut into pieces of n / 8 rows (not below 2^16) and each piece decides for itself,
+ * so with the default tunables a host call runs the equation from 2^21 elements, a ragged host call (one piece) from 2^18. */
+int ed25519_VerifyBatch_zip215_indexed_dev(void *result, const void *keys, size_t n_key, const void *key_index, const void *sig,
+                                           const void *msg, size_t msg_size, size_t n, const unsigned char *seed, void *stream);
+int ed25519_VerifyBatch_zip215_indexed_ragged_dev(void *result, const void *keys, size_t n_key, const void *key_index, const void *sig,
+                                                  const void *msgs, const uint64_t *offsets, size_t n, const unsigned char *seed,
+                                                  void *stream);
+int ed25519_VerifyBatch_zip215_indexed_batch(int *all_valid, int *verdict, const unsigned char *keys, size_t n_key,
+                                             const uint32_t *key_index, const unsigned char *sig, const unsigned char *msg,
+                                             size_t msg_size, size_t n, const unsigned char *seed);
+int ed25519_VerifyBatch_zip215_indexed_ragged_batch(int *all_valid, int *verdict, const unsigned char *keys, size_t n_key,
+                                                    const uint32_t *key_index, const unsigned char *sig, const unsigned char *msgs,
+                                                    const uint64_t *offsets, size_t n, const unsigned char *seed);
+/* bytes of device scratch the coalesced equation takes for n elements over n_key keys (N = n_key + n points; c, wa, wz, K buckets and
+ * r4 as for ed25519_VerifyBatch_scratch_bytes):
+ *   4 * (N * 40 + (K + wa + 1) * 40 + n * wz + n_key * wa + 16 * ceil(n / 256) + 16 * n_key + r4(N) + 2 K + 4)
+ * -- per element one packed row, one biased scalar, wz index entries and a flag: 204 bytes at c = 13; per key the same plus wa index
+ * entries and eight 64-bit sums: 308 bytes at c = 13. */
+size_t ed25519_VerifyBatch_indexed_scratch_bytes(size_t n, size_t n_key);
+
 /* ed25519_VerifySignature_* decide every element whose key decompresses onto the curve with an exact
  * lattice-shortened walk (csrc/verify_fast.cuh, ~134 doublings instead of 255) and run the reference's own operation
  * order only for the others (set C25519_AMD_VERIFY_REFERENCE_ORDER=1 to force it for everything).  This reports how many
@@ -457,6 +513,11 @@ int c25519_amd_verify_point_dev(void *out, const void *sig, const void *pk, cons
  * out: 32 bytes of device memory. */
 int c25519_amd_verify_batch_point_dev(void *out, const void *sig, const void *pk, const void *msg, size_t msg_size, size_t n,
                                       const unsigned char *seed, void *stream);
+/* the same for ed25519_VerifyBatch_zip215_indexed_*: enc(T) of the COALESCED point -- it may differ from the hook above's on the gathered
+ * keys by an 8-torsion point when a key has mixed order.  Elements with S >= L, an R or a named key that does not decode, or an index
+ * >= n_key are left out of the sums. */
+int c25519_amd_verify_batch_indexed_point_dev(void *out, const void *keys, size_t n_key, const void *key_index, const void *sig,
+                                              const void *msg, size_t msg_size, size_t n, const unsigned char *seed, void *stream);
 
 /* device field arithmetic on n pairs of 32-byte little-endian values taken mod p = 2^255-19 (host pointers):
  * out[i] = canonical(op(a[i], b[i])), op 0 mul, 1 square, 2 add, 3 sub, 4 inverse, 5 a^((p-5)/8),
