@@ -76,6 +76,12 @@ SIGNATURES = {
     "ed25519_Verify_Check_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
     "ed25519_Verify_Check_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
     "ed25519_Verify_Check_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_Verify_Check_zip215_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_Verify_Check_zip215_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_zip215_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_Verify_Check_zip215_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_Verify_Check_zip215_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_Blinding_Init_dev": [_vp, _vp, _sz, _vp],
     "ed25519_CreateKeyPair_blinded_batch": [_vp, _vp, _vp, _vp, _sz],
     "ed25519_CreateKeyPair_blinded_dev": [_vp, _vp, _vp, _vp, _sz, _vp],

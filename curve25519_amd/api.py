@@ -304,7 +304,13 @@ def ed25519_Verify_Check_strict(ctx, sig, msg):
     return ed25519_Verify_Check(ctx, sig, msg, strict=True)
 
 
-def ed25519_Verify_Check(ctx, sig, msg, strict=False):
+def ed25519_Verify_Check_zip215(ctx, sig, msg):
+    """The ZIP-215 verdict against one Verify_Init context: for a context that is Verify_Init's, ed25519_VerifySignature_zip215's
+    verdict under the context's key bytes 0..31 (include/curve25519_amd.h)."""
+    return ed25519_Verify_Check(ctx, sig, msg, rules="zip215")
+
+
+def ed25519_Verify_Check(ctx, sig, msg, strict=False, rules=None):
     """One key (a 2080-byte context), n (signature, message) pairs -> int32[n] verdicts."""
     ctx = np.ascontiguousarray(ctx, dtype=np.uint8).reshape(-1)
     if ctx.size != 2080:
@@ -313,7 +319,7 @@ def ed25519_Verify_Check(ctx, sig, msg, strict=False):
     n = sig.shape[0]
     msg, msg_size = _msgs(msg, n)
     ok = np.empty(n, np.int32)
-    name = "ed25519_Verify_Check_strict_batch" if strict else "ed25519_Verify_Check_batch"
+    name = f"ed25519_Verify_Check_{_RULES[rules or ('strict' if strict else 'plain')]}batch"
     _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(ctx), _ptr(sig), _ptr(msg), msg_size, n), name)
     return ok
 
@@ -326,7 +332,7 @@ def _ctx_index(ctxs, idx, n, width=2080, what="signature"):
     return ctxs, idx
 
 
-def ed25519_Verify_Check_indexed(ctxs, idx, sig, msg):
+def ed25519_Verify_Check_indexed(ctxs, idx, sig, msg, zip215=False):
     """Many keys in one call: uint8[n_ctx, 2080] contexts (Verify_Init's), uint32[n] indices, n (signature, message) pairs ->
     int32[n], element i checked against context idx[i] as ed25519_Verify_Check would.  An index >= n_ctx raises EngineError."""
     sig = _np(sig, 64, "sig")
@@ -334,12 +340,12 @@ def ed25519_Verify_Check_indexed(ctxs, idx, sig, msg):
     ctxs, idx = _ctx_index(ctxs, idx, n)
     msg, msg_size = _msgs(msg, n)
     ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_Verify_Check_indexed_batch(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig), _ptr(msg),
-                                                               msg_size, n), "ed25519_Verify_Check_indexed_batch")
+    name = "ed25519_Verify_Check_zip215_indexed_batch" if zip215 else "ed25519_Verify_Check_indexed_batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig), _ptr(msg), msg_size, n), name)
     return ok
 
 
-def ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages):
+def ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages, zip215=False):
     """ed25519_Verify_Check_indexed with per-element message lengths (`messages`: sequence of bytes-like)."""
     sig = _np(sig, 64, "sig")
     n = sig.shape[0]
@@ -348,10 +354,20 @@ def ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages):
         raise ValueError("one message per signature")
     flat, offsets = _ragged(messages)
     ok = np.empty(n, np.int32)
-    _lib.check(_lib.load().ed25519_Verify_Check_indexed_ragged_batch(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig),
-                                                                      _ptr(flat), _ptr(offsets), n),
-               "ed25519_Verify_Check_indexed_ragged_batch")
+    name = "ed25519_Verify_Check_zip215_indexed_ragged_batch" if zip215 else "ed25519_Verify_Check_indexed_ragged_batch"
+    _lib.check(getattr(_lib.load(), name)(_ptr(ok), _ptr(ctxs), ctxs.shape[0], _ptr(idx), _ptr(sig), _ptr(flat), _ptr(offsets), n), name)
     return ok
+
+
+def ed25519_Verify_Check_zip215_indexed(ctxs, idx, sig, msg):
+    """ed25519_Verify_Check_indexed under the ZIP-215 rule: element i gets ed25519_VerifySignature_zip215's verdict under the key bytes
+    of context idx[i], for contexts that are Verify_Init's (include/curve25519_amd.h).  An index >= n_ctx raises EngineError."""
+    return ed25519_Verify_Check_indexed(ctxs, idx, sig, msg, zip215=True)
+
+
+def ed25519_Verify_Check_zip215_indexed_ragged(ctxs, idx, sig, messages):
+    """ed25519_Verify_Check_zip215_indexed with per-element message lengths (`messages`: sequence of bytes-like)."""
+    return ed25519_Verify_Check_indexed_ragged(ctxs, idx, sig, messages, zip215=True)
 
 
 def ed25519_VerifyBatch_zip215_indexed(keys, idx, sig, msg, seed=None, verdicts=False):
@@ -515,7 +531,7 @@ def ed25519_SignMessage_indexed_dev(sig, ctxs, idx, msg):
         _lib.check(_lib.load().ed25519_SignMessage_indexed_dev(*args, msg.shape[1], n, st), "ed25519_SignMessage_indexed_dev")
 
 
-def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):
+def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg, zip215=False):
     """Device form of ed25519_Verify_Check_indexed: ctxs uint8[n_ctx, 2080], idx int32[n, 1] (read as uint32), verdict int32[n, 1].
     An index >= n_ctx gives verdict 0 (nothing is checked on the host)."""
     import torch
@@ -523,8 +539,41 @@ def ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg):
     args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(ctxs, 2080, "ctxs", device=d))
     args += (ctxs.shape[0], _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"),
              _check(msg, None, "msg", n, device=d))
+    name = "ed25519_Verify_Check_zip215_indexed_dev" if zip215 else "ed25519_Verify_Check_indexed_dev"
     with _on(sig) as st:
-        _lib.check(_lib.load().ed25519_Verify_Check_indexed_dev(*args, msg.shape[1], n, st), "ed25519_Verify_Check_indexed_dev")
+        _lib.check(getattr(_lib.load(), name)(*args, msg.shape[1], n, st), name)
+
+
+def ed25519_Verify_Check_zip215_indexed_dev(verdict, ctxs, idx, sig, msg):
+    """Device form of ed25519_Verify_Check_zip215_indexed (same tensors as ed25519_Verify_Check_indexed_dev)."""
+    ed25519_Verify_Check_indexed_dev(verdict, ctxs, idx, sig, msg, zip215=True)
+
+
+def ed25519_Verify_Check_zip215_indexed_ragged_dev(verdict, ctxs, idx, sig, flat, offsets):
+    """Device form with ragged messages: flat uint8[total, 1] message bytes, offsets int64[n + 1, 1] (read as uint64)."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(ctxs, 2080, "ctxs", device=d), ctxs.shape[0],
+            _check(idx, 1, "idx", n, dtype=torch.int32, device=d), _check(sig, 64, "sig"), _check(flat, 1, "flat", device=d),
+            _check(offsets, 1, "offsets", n + 1, dtype=torch.int64, device=d))
+    with _on(sig) as st:
+        _lib.check(_lib.load().ed25519_Verify_Check_zip215_indexed_ragged_dev(*args, n, st), "ed25519_Verify_Check_zip215_indexed_ragged_dev")
+
+
+def ed25519_Verify_Check_dev(verdict, ctx, sig, msg, rules="plain"):
+    """Device form of ed25519_Verify_Check (rules: "plain", "strict", "zip215"): ctx uint8[1, 2080] on the device, verdict int32[n, 1]."""
+    import torch
+    n, d = sig.shape[0], sig.device
+    args = (_check(verdict, 1, "verdict", n, dtype=torch.int32, device=d), _check(ctx, 2080, "ctx", 1, device=d), _check(sig, 64, "sig"),
+            _check(msg, None, "msg", n, device=d))
+    name = f"ed25519_Verify_Check_{_RULES[rules]}dev"
+    with _on(sig) as st:
+        _lib.check(getattr(_lib.load(), name)(*args, msg.shape[1], n, st), name)
+
+
+def ed25519_Verify_Check_zip215_dev(verdict, ctx, sig, msg):
+    """Device form of ed25519_Verify_Check_zip215: ctx uint8[1, 2080] on the device, verdict int32[n, 1]."""
+    ed25519_Verify_Check_dev(verdict, ctx, sig, msg, "zip215")
 
 
 def _verify_dev(verdict, sig, pk, msg, rules):

@@ -585,13 +585,13 @@ static int verify_check_batch(int* verdict, const void* ctx, const unsigned char
 {
     C25519_API_CALL();
     if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
-    if (rules == RULES_ZIP215) return bad_arg("internal: ed25519_Verify_Check has no ZIP-215 form");
     if (n == 0) return 0;
     ThreadState& t = tls();
     C25519_RC(t.ensure());
     void* dctx = nullptr;                                   // (one Verify_Init and MANY Verify_Check calls on the same context: a kept record)
     C25519_RC(t.vctx.device_copy(&dctx, ctx));
-    const auto check_dev = rules == RULES_STRICT ? ed25519_Verify_Check_strict_dev : ed25519_Verify_Check_dev;
+    const auto check_dev = rules == RULES_STRICT ? ed25519_Verify_Check_strict_dev
+                         : rules == RULES_ZIP215 ? ed25519_Verify_Check_zip215_dev : ed25519_Verify_Check_dev;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ msg, nullptr, msg_size }, Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
                          return check_dev(d[2], dctx, d[0], d[1], msg_size, c, st);
@@ -610,33 +610,66 @@ int ed25519_Verify_Check_strict_batch(int* verdict, const void* ctx, const unsig
     return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, RULES_STRICT);
 }
 
-int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
-                                       const unsigned char* sig, const unsigned char* msg, size_t msg_size, size_t n)
+int ed25519_Verify_Check_zip215_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg,
+                                      size_t msg_size, size_t n)
+{
+    return verify_check_batch(verdict, ctx, sig, msg, msg_size, n, RULES_ZIP215);
+}
+
+// (the plain and the ZIP-215 form: the same contexts in the same kept buffer, the same index check, the same pieces)
+static int verify_check_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index, const unsigned char* sig,
+                                      const unsigned char* msg, size_t msg_size, size_t n, bool zip215)
 {
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
     if (n == 0) return 0;
     void* dctxs = nullptr;
     C25519_RC(indexed_prepare(&dctxs, tls().vctxs, 2080, ctxs, n_ctx, ctx_index, n));
+    const auto check_dev = zip215 ? ed25519_Verify_Check_zip215_indexed_dev : ed25519_Verify_Check_indexed_dev;
     return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ msg, nullptr, msg_size },
                           Arr{ nullptr, verdict, sizeof(int) } },
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_Verify_Check_indexed_dev(d[3], dctxs, n_ctx, d[1], d[0], d[2], msg_size, c, st);
+                         return check_dev(d[3], dctxs, n_ctx, d[1], d[0], d[2], msg_size, c, st);
                      });
 }
 
-int ed25519_Verify_Check_indexed_ragged_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
-                                              const unsigned char* sig, const unsigned char* msgs, const uint64_t* offsets, size_t n)
+static int verify_check_indexed_ragged_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index, const unsigned char* sig,
+                                             const unsigned char* msgs, const uint64_t* offsets, size_t n, bool zip215)
 {
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
     if (n == 0) return 0;
     void* dctxs = nullptr;
     C25519_RC(indexed_prepare(&dctxs, tls().vctxs, 2080, ctxs, n_ctx, ctx_index, n));
+    const auto check_dev = zip215 ? ed25519_Verify_Check_zip215_indexed_ragged_dev : ed25519_Verify_Check_indexed_ragged_dev;
     return run_ragged(n, { Arr{ sig, nullptr, 64 }, Arr{ ctx_index, nullptr, sizeof(uint32_t) }, Arr{ nullptr, verdict, sizeof(int) } },
                       msgs, offsets, [&](void** d, hipStream_t st) -> int {
-                          return ed25519_Verify_Check_indexed_ragged_dev(d[2], dctxs, n_ctx, d[1], d[0], d[3], (const uint64_t*)d[4], n, st);
+                          return check_dev(d[2], dctxs, n_ctx, d[1], d[0], d[3], (const uint64_t*)d[4], n, st);
                       });
+}
+
+int ed25519_Verify_Check_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                       const unsigned char* sig, const unsigned char* msg, size_t msg_size, size_t n)
+{
+    return verify_check_indexed_batch(verdict, ctxs, n_ctx, ctx_index, sig, msg, msg_size, n, false);
+}
+
+int ed25519_Verify_Check_indexed_ragged_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                              const unsigned char* sig, const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    return verify_check_indexed_ragged_batch(verdict, ctxs, n_ctx, ctx_index, sig, msgs, offsets, n, false);
+}
+
+int ed25519_Verify_Check_zip215_indexed_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                              const unsigned char* sig, const unsigned char* msg, size_t msg_size, size_t n)
+{
+    return verify_check_indexed_batch(verdict, ctxs, n_ctx, ctx_index, sig, msg, msg_size, n, true);
+}
+
+int ed25519_Verify_Check_zip215_indexed_ragged_batch(int* verdict, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
+                                                     const unsigned char* sig, const unsigned char* msgs, const uint64_t* offsets, size_t n)
+{
+    return verify_check_indexed_ragged_batch(verdict, ctxs, n_ctx, ctx_index, sig, msgs, offsets, n, true);
 }
 
 int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)

@@ -3,6 +3,7 @@
 // (one of the engine's four translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 #include "verify_ctx.cuh"
+#include "verify_ctx_zip215.cuh"
 
 // ed25519_Verify_Init (ed25519_verify.c:179-232): decompress -A (inverted parity :192-195, no validation) and
 // fill the key's 16-row 4-fold table.  `tables` holds n tables of Tbl's format, `stride_words` apart.
@@ -813,6 +814,47 @@ __global__ void __launch_bounds__(ED_BLOCK, 2) k_ed25519_verify_slow_zip215(Fast
     if (k == 0) signal_done(done);
 }
 
+// ---- ed25519_Verify_Check_zip215_*: the ZIP-215 verdict against Verify_Init contexts (verify_ctx_zip215.cuh) ------------------------------
+// Behind the plain calls' own walk kernels, which are launched as the plain calls launch them (no twin of a walk: a twin in this unit
+// has changed their gfx950 code before).  k_ed25519_verify_coset_prep, one launch of two roles: the first `elem_blocks`
+// workgroups take an element per lane and turn the T the walk left into W = Z (Z^2 + kXY)(Z^2 - kXY), in the scratch part the shared
+// inversion is then pointed at (ProjScratch::prefix); the others take a CONTEXT per lane and decide rule 2 for it, one word each.
+// k_batch_invert<FinishVerifyZip215> then compares the coset T + E[8] with R's bytes and writes the verdicts.
+constexpr int ZC_BLOCK = 256;
+__global__ void __launch_bounds__(ZC_BLOCK) k_ed25519_verify_coset_prep(ProjScratch scr, size_t n, unsigned elem_blocks,
+                                                                               const u32* __restrict__ ctxs, size_t n_ctx, u32* key_ok)
+{
+    if (blockIdx.x < elem_blocks) {
+        const size_t i = (size_t)blockIdx.x * ZC_BLOCK + threadIdx.x;
+        if (i < n) coset_prep_element(scr.prefix, scr.a, scr.b, scr.z, n, i);
+        return;
+    }
+    const size_t c = (size_t)(blockIdx.x - elem_blocks) * ZC_BLOCK + threadIdx.x;
+    if (c < n_ctx) key_ok[c] = zip215_ctx_key_ok(ctxs + c * VCTX_WORDS);
+}
+
+// calls below ZIP215_CHECK_MIN: pk[i] = bytes 0..31 of element i's context (ctx_index null: of the one context) for
+// ed25519_VerifySignature_zip215_dev's kernels -- the same verdict for a context that is Verify_Init's; an index out of range takes
+// context 0, and k_ed25519_verify_coset_index_mask writes its verdict 0 afterwards
+__global__ void __launch_bounds__(ZC_BLOCK) k_ed25519_verify_coset_key_gather(void* pk, const u32* __restrict__ ctxs, size_t n_ctx,
+                                                                               const u32* __restrict__ ctx_index, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * ZC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 k = ctx_index ? ctx_index[i] : 0u;
+    const u32* ctx = ctxs + (size_t)(k < n_ctx ? k : 0u) * VCTX_WORDS;
+    u32 w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = ctx[j];
+    store32(pk, i, w);
+}
+
+__global__ void __launch_bounds__(ZC_BLOCK) k_ed25519_verify_coset_index_mask(int* verdict, const u32* __restrict__ ctx_index, size_t n_ctx, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * ZC_BLOCK + threadIdx.x;
+    if (i < n && ctx_index[i] >= n_ctx) verdict[i] = 0;
+}
+
 namespace {
 
 // scratch of one verification pass: per-lane tables (the larger of the two paths' formats: they never live at the same
@@ -1011,6 +1053,64 @@ int ed25519_VerifySignature_zip215_ragged_dev(void* verdict, const void* sig, co
     return verify_dev(verdict, sig, pk, ragged_msgs(msgs, offsets), n, (hipStream_t)stream, RULES_ZIP215);
 }
 
+// ---- ed25519_Verify_Check_zip215_*: host side (the kernels: above, behind the lattice path's ZIP-215 twins) --------------------------------
+// The smallest call that walks the contexts (tunable ZIP215_CHECK_MIN; 0 = always): below it the per-lane context kernels lose to
+// ed25519_VerifySignature_zip215_dev's per-wave and quad paths on the gathered keys, which give the same verdict for a context that
+// is Verify_Init's.  The default is NOT yet set from this call's own cells (tools/verify_check_zip215_rate.py has not been run on a
+// device: DESIGN.md, "ZIP-215 against contexts"): it is the smallest size at which the plain pair was measured with the context path
+// ahead -- ed25519_Verify_Check_indexed_dev against ed25519_VerifySignature_dev, profiles/indexed_check_rate.txt: 0.82-0.89 x up to
+// 2^14, 1.66-1.84 x at 2^16, nothing measured in between -- and both sides of this call run those kernels plus a few percent.
+constexpr long ZIP215_CHECK_MIN_DEFAULT = 1L << 16;
+static bool zip215_check_walks(size_t n)
+{
+    const long mn = c25519_host::tunable_or(c25519_host::T_ZIP215_CHECK_MIN, ZIP215_CHECK_MIN_DEFAULT);
+    return mn <= 0 || n >= (size_t)mn;
+}
+
+// behind a walk that left T in `scr`: coset prep (and rule 2 for the call's contexts, into key_ok), then the shared inversion over the
+// prep's products with the coset comparison as its finish
+static int launch_coset_finish(const ProjScratch& scr, size_t n, const u32* ctxs, size_t n_ctx, const u32* ctx_index, u32* key_ok,
+                               const void* sig, int* verdict, hipStream_t stream)
+{
+    const unsigned eb = grid_for(n, ZC_BLOCK);
+    k_ed25519_verify_coset_prep<<<eb + grid_for(n_ctx, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(scr, n, eb, ctxs, n_ctx, key_ok);
+    C25519_TRY(hipGetLastError());
+    // This finish keeps more alive per element than the byte comparisons do: with 14 and 16 elements per lane the allocator spilled
+    // (34 registers, 656 bytes of scratch per lane), so it is instantiated up to 12 (what 16 buys elsewhere: 9.29 against 9.33 ms per pass)
+    const FinishVerifyZip215 fin{ scr.a, scr.b, scr.z, sig, verdict, n, ctx_index, n_ctx, key_ok };
+    const int K = inversion_group(std::min(inversion_k(n), 12));
+    const size_t m = (n + K - 1) / K;
+    const unsigned grid = grid_for(m, INV_BLOCK);
+    switch (K) {
+        case 12: k_batch_invert<FinishVerifyZip215, 12><<<grid, INV_BLOCK, 0, stream>>>(scr.prefix, nullptr, n, m, fin); break;
+        case 8:  k_batch_invert<FinishVerifyZip215, 8><<<grid, INV_BLOCK, 0, stream>>>(scr.prefix, nullptr, n, m, fin); break;
+        case 4:  k_batch_invert<FinishVerifyZip215, 4><<<grid, INV_BLOCK, 0, stream>>>(scr.prefix, nullptr, n, m, fin); break;
+        case 2:  k_batch_invert<FinishVerifyZip215, 2><<<grid, INV_BLOCK, 0, stream>>>(scr.prefix, nullptr, n, m, fin); break;
+        default: k_batch_invert<FinishVerifyZip215, 1><<<grid, INV_BLOCK, 0, stream>>>(scr.prefix, nullptr, n, m, fin); break;
+    }
+    C25519_TRY(hipGetLastError());
+    return 0;
+}
+
+// the keys gathered behind the per-element call's scratch, then that call (ctx_index null: one context)
+static int zip215_check_gathered(int* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig, Msgs msgs, size_t n,
+                                 hipStream_t stream)
+{
+    const size_t inner = round_up(ed25519_VerifySignature_scratch_bytes(n), 256);
+    void* w = nullptr;
+    c25519_host::WorkLease lease;
+    C25519_RC(lease.acquire(&w, inner + n * 32, stream));
+    void* pk = (char*)w + inner;
+    k_ed25519_verify_coset_key_gather<<<grid_for(n, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(pk, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
+    C25519_TRY(hipGetLastError());
+    C25519_RC(verify_dev(verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false));
+    if (ctx_index) {
+        k_ed25519_verify_coset_index_mask<<<grid_for(n, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(verdict, (const u32*)ctx_index, n_ctx, n);
+        C25519_TRY(hipGetLastError());
+    }
+    return lease.release();
+}
+
 // two-phase verification on the device: contexts are 2080-byte records (pk || 16 x 128-byte canonical rows),
 // the reference's EDP_SIGV_CTX size and row order.
 int ed25519_Verify_Init_dev(void* ctx, const void* pk, size_t n, void* stream)
@@ -1030,14 +1130,11 @@ int ed25519_Verify_Init_dev(void* ctx, const void* pk, size_t n, void* stream)
     return 0;
 }
 
-int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, const void* msg, size_t msg_size,
-                             size_t n, void* stream_)
+// zip215: ed25519_Verify_Check_zip215_dev above ZIP215_CHECK_MIN -- the same walk (never the per-wave or the quad kernel, which write
+// plain verdicts themselves: a remembered comb is walked by the lane kernel at every size), the coset comparison instead of FinishVerify
+static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig, const void* msg, size_t msg_size, size_t n,
+                                hipStream_t stream, bool zip215)
 {
-    C25519_API_CALL();
-    if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
-    if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
-    if (n == 0) return 0;
-    hipStream_t stream = (hipStream_t)stream_;
     const Msgs msgs = fixed_msgs(msg, msg_size);
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
@@ -1053,7 +1150,7 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     const bool try_wide = build || reuse;
     tl_last_check = LastCheck();
     tl_last_check.ran = true;
-    if (!try_wide && small) {                               // a few pairs: one per wave, the reference's order
+    if (!zip215 && !try_wide && small) {                    // a few pairs: one per wave, the reference's order
         k_ed25519_verify_check_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctx, msgs, n, tbl, take_done_word(n));
         C25519_TRY(hipGetLastError());
         return 0;
@@ -1087,7 +1184,7 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
             k_ed25519_verify_ctx_remember<<<1, 128, 0, stream>>>(remembered, (const u32*)ctx, wide_ok);
             C25519_TRY(hipGetLastError());
         }
-        quads = one_key_quad_for(n);
+        quads = !zip215 && one_key_quad_for(n);
         if (quads)                                          // four lanes per pair, the verdict in the same launch
             k_ed25519_verify_check_wide_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(
                 (int*)verdict, sig, (const u32*)ctx, msgs, n, wide_base, wide_key, wide_ok);
@@ -1099,10 +1196,25 @@ int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, co
     k_ed25519_verify_check_shared<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
         scr, sig, (const u32*)ctx, msgs, n, tbl, wide_ok);
     C25519_TRY(hipGetLastError());
-    // (the quad kernel has written the verdicts itself where the combs decided: the shared inversion then finds wide_ok set and leaves)
-    C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
+    if (zip215) {                                           // rule 2 for the one context: word 1 behind the projective part
+        u32* key_ok = (u32*)w + proj_words(n) + 1;
+        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctx, 1, nullptr, key_ok, sig, (int*)verdict, stream));
+    } else {
+        // (the quad kernel has written the verdicts itself where the combs decided: the shared inversion then finds wide_ok set and leaves)
+        C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
+    }
     C25519_RC(keep_lease.release());
     return lease.release();
+}
+
+int ed25519_Verify_Check_dev(void* verdict, const void* ctx, const void* sig, const void* msg, size_t msg_size,
+                             size_t n, void* stream_)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
+    if (n == 0) return 0;
+    return verify_check_one_dev(verdict, ctx, sig, msg, msg_size, n, (hipStream_t)stream_, false);
 }
 
 // ed25519_Verify_Check_dev under the strict rules: the plain call, then k_ed25519_verify_check_strict_mask on the same stream
@@ -1124,15 +1236,18 @@ int ed25519_Verify_Check_strict_dev(void* verdict, const void* ctx, const void* 
 
 // n x ed25519_Verify_Check(ctxs + 2080 * ctx_index[i], pair i): up to COOP_MAX pairs (default 1024) one per wave, above that one per
 // lane and the shared inversion.  An index >= n_ctx gives verdict 0 (the device cannot refuse the call without a synchronise).
+// zip215: ed25519_Verify_Check_zip215_indexed_dev -- below ZIP215_CHECK_MIN the per-element call on the gathered keys; from there
+// the lane kernel at every size and the coset comparison instead of FinishVerifyIndexed
 static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig, Msgs msgs,
-                                    size_t n, hipStream_t stream)
+                                    size_t n, hipStream_t stream, bool zip215 = false)
 {
     if (int rc = check_dev_args(n, { verdict, ctxs, ctx_index, sig })) return rc;
     if (n == 0) return 0;
     if (n_ctx == 0) return bad_arg("no contexts");
+    if (zip215 && !zip215_check_walks(n)) return zip215_check_gathered((int*)verdict, ctxs, n_ctx, ctx_index, sig, msgs, n, stream);
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
-    if (coop_for(n, 1024)) {
+    if (!zip215 && coop_for(n, 1024)) {
         k_ed25519_verify_check_indexed_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctxs, n_ctx,
                                                                             (const u32*)ctx_index, msgs, n, tbl, take_done_word(n));
         C25519_TRY(hipGetLastError());
@@ -1141,7 +1256,7 @@ static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ct
     const size_t row_words = C25519_INDEXED_REPACK ? n_ctx * QTABLE_CANON_WORDS : 0;
     void* w = nullptr;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, (row_words + proj_words(n)) * sizeof(u32), stream));
+    C25519_RC(lease.acquire(&w, (row_words + proj_words(n) + (zip215 ? round_up(n_ctx, 4) : 0)) * sizeof(u32), stream));
     u32* rows = (u32*)w;                                    // first in the slab (hipMalloc: 256-byte aligned): whole 128-byte rows
     const ProjScratch scr = carve_proj(rows + row_words, n);
 #if C25519_INDEXED_REPACK
@@ -1151,7 +1266,11 @@ static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ct
     k_ed25519_verify_check_indexed<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(scr, sig, (const u32*)ctxs, n_ctx, (const u32*)ctx_index,
                                                                                   msgs, n, tbl, rows);
     C25519_TRY(hipGetLastError());
-    C25519_RC(launch_invert(scr, n, FinishVerifyIndexed{ scr.a, scr.b, sig, (int*)verdict, n, (const u32*)ctx_index, n_ctx }, stream));
+    if (zip215)                                             // rule 2 per context: n_ctx words behind the projective part
+        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, rows + row_words + proj_words(n), sig,
+                                      (int*)verdict, stream));
+    else
+        C25519_RC(launch_invert(scr, n, FinishVerifyIndexed{ scr.a, scr.b, sig, (int*)verdict, n, (const u32*)ctx_index, n_ctx }, stream));
     return lease.release();
 }
 
@@ -1169,6 +1288,38 @@ int ed25519_Verify_Check_indexed_ragged_dev(void* verdict, const void* ctxs, siz
     C25519_API_CALL();
     if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
     return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, ragged_msgs(msgs, offsets), n, (hipStream_t)stream);
+}
+
+// the ZIP-215 verdict against contexts (include/curve25519_amd.h): arguments and argument errors of the plain calls they are named after
+int ed25519_Verify_Check_zip215_dev(void* verdict, const void* ctx, const void* sig, const void* msg, size_t msg_size,
+                                    size_t n, void* stream_)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctx || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
+    if (n == 0) return 0;
+    if (!zip215_check_walks(n)) {
+        tl_last_check = LastCheck();
+        tl_last_check.ran = true;
+        return zip215_check_gathered((int*)verdict, ctx, 1, nullptr, sig, fixed_msgs(msg, msg_size), n, (hipStream_t)stream_);
+    }
+    return verify_check_one_dev(verdict, ctx, sig, msg, msg_size, n, (hipStream_t)stream_, true);
+}
+
+int ed25519_Verify_Check_zip215_indexed_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig,
+                                            const void* msg, size_t msg_size, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctxs || !ctx_index || !sig || (!msg && msg_size)) return bad_arg("null pointer");
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, fixed_msgs(msg, msg_size), n, (hipStream_t)stream, true);
+}
+
+int ed25519_Verify_Check_zip215_indexed_ragged_dev(void* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig,
+                                                   const void* msgs, const uint64_t* offsets, size_t n, void* stream)
+{
+    C25519_API_CALL();
+    if (!verdict || !ctxs || !ctx_index || !sig || !offsets) return bad_arg("null pointer");
+    return verify_check_indexed_dev(verdict, ctxs, n_ctx, ctx_index, sig, ragged_msgs(msgs, offsets), n, (hipStream_t)stream, true);
 }
 
 // test / accounting hook: did the calling thread's last ed25519_Verify_Check_* call on this device walk the two wide combs (1), or

@@ -471,6 +471,44 @@ int ed25519_Verify_Check_indexed_ragged_batch(int *verdict, const void *ctxs, si
 int ed25519_Verify_Check_indexed_ragged_dev(void *verdict, const void *ctxs, size_t n_ctx, const void *ctx_index,
                                             const void *sig, const void *msgs, const uint64_t *offsets, size_t n, void *stream);
 
+/* The ZIP-215 verdict (rules 1-4 above ed25519_VerifySignature_zip215_batch) against Verify_Init contexts: one context, or many
+ * contexts and a mixed stream of triples.  Argument lists, layouts, argument errors, the host-side index check, the once-per-call
+ * context upload, stream behaviour and n == 0 are those of the plain calls they are named after; contexts are ed25519_Verify_Init_*'s
+ * 2080-byte records (no new context type, no new Init call).
+ *   Contract: for a context that is byte for byte what Verify_Init writes for its first 32 bytes, element i's verdict equals
+ *   ed25519_VerifySignature_zip215_*'s for (sig_i, those 32 bytes, msg_i) -- for every input: small-order, mixed-order,
+ *   non-canonical and undecodable keys and R's included.  Any other context is the caller's own trusted storage, as for the plain
+ *   calls: its verdict is unspecified (0 or 1), and nothing outside ctxs is read.  *_dev: an index >= n_ctx gives verdict 0;
+ *   *_batch: such an index refuses the call before any work, verdict untouched.
+ * How: the plain calls' own walk kernels leave T = [S]B - [k]A; rule 4, [8](T - R) = O, says that R lies in the coset T + E[8], so
+ * R's bytes are compared with the eight points T + t -- y_R = (low 255 bits) mod p against their y, bit 255 against the parity of
+ * their x (ignored for x = 0) -- behind ONE shared inversion per element: no square root of R, no extra doublings
+ * (csrc/verify_ctx_zip215.cuh).  Rule 2 is decided once per context from its row 1 (the curve equation), rule 1 per pair.
+ * Dispatch: calls of at least ZIP215_CHECK_MIN pairs (tunable; default 2^16; 0 = always) walk the contexts one pair per lane --
+ * one context: the shared-table kernel, or the two wide combs from ONE_KEY_WIDE pairs or with a remembered comb (kept with, and
+ * shared with, ed25519_Verify_Check_*'s; c25519_amd_verify_check_last_wide() reports it; the four-lane kernel of the plain call's
+ * 2^10..2^14 range is not used).  Smaller calls gather bytes 0..31 of each element's context and run
+ * ed25519_VerifySignature_zip215_dev's kernels: the same verdict by the contract.
+ * Measured on MI355X (tools/verify_check_zip215_rate.py, profiles/verify_check_zip215_rate.txt): NOT MEASURED YET -- no device
+ * was reached while these calls were built, so the tool has not produced its table and the default of ZIP215_CHECK_MIN is the plain
+ * pair's measured crossover (csrc/engine_verify.hip: ZIP215_CHECK_MIN_DEFAULT), not this call's own.  By operation count (5 + 21
+ * products and 9 canonicalisations per pair behind a walk of ~1 200 products) the context path should run within a few percent of the
+ * plain context calls -- 204-219 M/s over many contexts, 646-664 M/s over one key at 2^20, about 1.8 x
+ * ed25519_VerifySignature_zip215_* over many keys; that is a count, not a result. */
+int ed25519_Verify_Check_zip215_batch(int *verdict, const void *ctx, const unsigned char *sig,
+                                      const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_Verify_Check_zip215_dev(void *verdict, const void *ctx, const void *sig, const void *msg,
+                                    size_t msg_size, size_t n, void *stream);
+int ed25519_Verify_Check_zip215_indexed_batch(int *verdict, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                              const unsigned char *sig, const unsigned char *msg, size_t msg_size, size_t n);
+int ed25519_Verify_Check_zip215_indexed_dev(void *verdict, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                            const void *sig, const void *msg, size_t msg_size, size_t n, void *stream);
+int ed25519_Verify_Check_zip215_indexed_ragged_batch(int *verdict, const void *ctxs, size_t n_ctx, const uint32_t *ctx_index,
+                                                     const unsigned char *sig, const unsigned char *msgs, const uint64_t *offsets,
+                                                     size_t n);
+int ed25519_Verify_Check_zip215_indexed_ragged_dev(void *verdict, const void *ctxs, size_t n_ctx, const void *ctx_index,
+                                                   const void *sig, const void *msgs, const uint64_t *offsets, size_t n, void *stream);
+
 /* Multi-GPU (BASELINE.json north_star: "batches shard embarrassingly across the 8 GPUs of one node
  * with a single RCCL gather over xGMI") ------------------------------------------------------------------------------
  * A handle owns ONE WORKER THREAD PER DEVICE.  A call cuts the batch into contiguous shards (device d owns elements

@@ -576,6 +576,34 @@ def main():
     mul(t2d_neg, CANON, "signed comb: ge_from_pa T of a negated first row")
     carry32(neg(CANON, "signed comb table generation: -B's 2dxy"))
     print("lattice verification walk, signed comb and blinded base walk: ok")
+    # ---- verify_ctx_zip215.cuh: the coset comparison behind the context walks (X, Y, Z reduced: the walk's last products) ----
+    def coset_denominators(X, Y, Z):
+        zz = sqr(Z, "coset Z^2")
+        kxy = mul(mul(X, Y, "coset XY"), CANON, "coset kXY")
+        return add(zz, kxy), sub(zz, kxy, "coset dm")
+
+    dp, dm = coset_denominators(R, R, R)
+    W = mul(mul(dm, dp, "coset prep dm*dp"), R, "coset prep W")                    # coset_prep_element
+    need(all(W[i] <= R[i] for i in range(10)), "coset prep: W not reduced")
+    w_inv = R                                                                       # the shared inversion's output: a product, or zero
+    to_words(w_inv, "coset w_inv to_words")
+    z_inv = mul(mul(dm, dp, "coset dm*dp"), w_inv, "coset 1/Z")                     # coset_contains_r
+    t = mul(mul(w_inv, R, "coset w_inv*Z"), R, "coset w_inv*Z^2")
+    zdp, zdm = mul(dm, t, "coset Z/dp"), mul(dp, t, "coset Z/dm")
+    x, y = mul(R, z_inv, "coset x"), mul(R, z_inv, "coset y")
+    for v in (x, y, mul(y, CANON, "coset i*y"), mul(x, CANON, "coset i*x")):
+        to_words(v, "coset candidate to_words")
+    a, b = mul(R, CANON, "coset X*y8"), mul(R, CANON, "coset Y*x8")
+    for num, den in ((add(a, b), zdp), (add(a, b), zdm), (sub(a, b, "coset a-b"), zdm), (sub(a, b, "coset c-e"), zdp)):
+        to_words(mul(num, den, "coset candidate of the order-8 family"), "coset candidate to_words")
+    # zip215_ctx_key_ok: the curve equation on row 1 of a context (its fields read by fe_from_words), and its y against the key's
+    x2, y2 = sub(FROM_WORDS, FROM_WORDS, "key_ok 2x"), add(FROM_WORDS, FROM_WORDS)
+    xx, yy = sqr(x2, "key_ok (2x)^2"), sqr(y2, "key_ok (2y)^2")
+    lhs = chained_small_mul(sub(yy, xx, "key_ok yy-xx"), 4, [0] * 10, "key_ok 4(yy-xx)")
+    rhs = add(mul(mul(xx, yy, "key_ok xx*yy"), CANON, "key_ok d*xx*yy"), [16] + [0] * 9)
+    to_words(sub(lhs, rhs, "key_ok lhs-rhs"), "key_ok curve equation to_words")
+    to_words(sub(y2, carry32(add(FROM_WORDS, FROM_WORDS), "key_ok 2 y_key"), "key_ok y"), "key_ok y to_words")
+    print("ZIP-215 coset comparison against contexts (prep, finish, rule 2 per context): ok")
     quad_section(R)
     print("quad25519 ladder step, addition, doubling, batch-inversion exchange: ok")
     small = coop_section(R)
