@@ -1,5 +1,8 @@
-"""Builds tests/host_emul/libc25519_emul.so: the device headers of curve25519_amd/csrc compiled by g++ against the C
-model of the gfx950 primitives (valu_model.h).  TEST INFRASTRUCTURE -- see valu_model.h."""
+"""Builds the host-emulation libraries of tests/host_emul: device headers of curve25519_amd/csrc compiled by g++ against the C model
+of the gfx950 primitives (valu_model.h).  build() gives libc25519_emul.so (emul.cpp), build_lib() any of them; open_lib() loads one
+for a test.  A library is rebuilt when a file the compiler read for it (its -MMD list, kept next to it as <lib>.d) has changed.
+TEST INFRASTRUCTURE -- see valu_model.h."""
+import ctypes
 import os
 import subprocess
 
@@ -7,21 +10,58 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "curve25519_amd", "csrc")
 LIB = os.path.join(HERE, "libc25519_emul.so")
-HEADERS = ["valu_gfx950.cuh", "safegcd25519.cuh", "fe25519.cuh", "sc25519.cuh", "sha512.cuh", "ge25519.cuh", "x25519.cuh", "lanes.cuh",
-           "curve_constants.cuh", "verify_fast.cuh", "coop25519.cuh", "coop_ops.cuh", "quad25519.cuh", "batch_invert.cuh",
-           "batch_invert_lane.inc"]
+# run in HERE with relative paths, so that the dependency file names relative paths and holds wherever the tree is copied
+CXX = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
+       "-include", "valu_model.h", "-I", "../../curve25519_amd/csrc", "-I", "."]
+MAD_OVERFLOW = "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+
+
+def stale(lib: str) -> bool:
+    """the library or its dependency file is missing, or a file named there (the source and valu_model.h among them) is missing or
+    newer than the library"""
+    if not (os.path.exists(lib) and os.path.exists(lib + ".d")):
+        return True
+    with open(lib + ".d") as f:
+        deps = f.read().replace("\\\n", " ").partition(":")[2].split()
+    built = os.path.getmtime(lib)
+    deps = [os.path.join(HERE, d) for d in deps]
+    return not deps or any(not os.path.exists(d) or os.path.getmtime(d) > built for d in deps)
+
+
+def build_lib(source: str, lib_name: str, extra_include_dirs=(), force: bool = False) -> str:
+    """tests/host_emul/<source> -> tests/host_emul/<lib_name>, if it is stale or force is set; returns the library's path"""
+    lib = os.path.join(HERE, lib_name)
+    if not force and not stale(lib):
+        return lib
+    tmp, dep = f"{lib_name}.tmp.{os.getpid()}", f"{lib_name}.d.tmp.{os.getpid()}"
+    includes = [a for d in extra_include_dirs for a in ("-I", os.path.relpath(d, HERE))]
+    subprocess.check_call([*CXX, *includes, "-MMD", "-MF", dep, source, "-o", tmp, "-lpthread"], cwd=HERE)
+    os.replace(os.path.join(HERE, dep), lib + ".d")
+    os.replace(os.path.join(HERE, tmp), lib)
+    return lib
 
 
 def build(force: bool = False) -> str:
-    srcs = [os.path.join(HERE, f) for f in ("emul.cpp", "valu_model.h", "coop_wave.h")] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in srcs):
-        return LIB
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "emul.cpp"),
-           "-o", LIB + ".tmp", "-lpthread"]
-    subprocess.check_call(cmd)
-    os.replace(LIB + ".tmp", LIB)
-    return LIB
+    return build_lib("emul.cpp", os.path.basename(LIB), force=force)
+
+
+def open_lib(functions=None, source: str = "emul.cpp", lib_name: str = os.path.basename(LIB), extra_include_dirs=(), mad_counter: bool = True):
+    """Builds the library if needed and opens it.  functions: {name: argtypes} or {name: (argtypes, restype)}; a name given without
+    a restype keeps ctypes' int.  mad_counter: the library has valu_model.h's overflow counter (every one that multiplies does)."""
+    lib = ctypes.CDLL(build_lib(source, lib_name, extra_include_dirs))
+    if mad_counter:
+        lib.emul_mad_overflow_count.restype = ctypes.c_ulonglong
+    for name, sig in (functions or {}).items():
+        fn = getattr(lib, name)
+        if isinstance(sig, tuple):
+            fn.argtypes, fn.restype = sig
+        else:
+            fn.argtypes = sig
+    return lib
+
+
+def assert_no_mad_overflow(lib):
+    assert lib.emul_mad_overflow_count() == 0, MAD_OVERFLOW
 
 
 if __name__ == "__main__":

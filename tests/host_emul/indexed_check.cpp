@@ -4,7 +4,7 @@
 // or over the 128-byte-aligned copy k_ed25519_verify_ctx_repack makes), the projective results in the scratch's SoA layout, then
 // k_batch_invert<FinishVerifyIndexed, K>'s lanes (csrc/batch_invert_lane.inc) in workgroups of 64 lock-step lanes.  The contexts are
 // copied into a buffer of exactly n_ctx x 2080 bytes first, so that a build with -fsanitize=address sees a read past them.
-// Built into its own library by tests/test_host_emul_indexed_check.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_indexed_check.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #define EMUL_COOP_WAVE_IMPL 1
 #include "coop_wave.h"

@@ -3,8 +3,8 @@
 // comb from k_x25519_peer_prepare's ge_signed_comb_row_of at the offsets that kernel writes them to, and k_x25519_one_peer_mult's
 // x25519_one_peer_lane over them; the shared inversion is a plain fe_invert.  A comb row costs ~2400 field operations in the
 // C model, so only the rows the secrets of a call select are generated (all of them would be 16384 per peer); the walk reads
-// them from a full-size table in the device layout.  Built into its own library by tests/test_host_emul_one_peer.py with
-// the recipe of tests/host_emul/build.py.  Not part of the product.
+// them from a full-size table in the device layout.  Built into its own library by tests/test_host_emul_one_peer.py through
+// tests/host_emul/build.py's build_lib.  Not part of the product.
 #define EMUL_COOP_WAVE_IMPL 1
 #include "coop_wave.h"
 #include "lanes.cuh"

@@ -4,7 +4,7 @@
 // ladder list for an ineligible context, peer_ctx_columns + peer_ctx_walk over the context's rows in place), k_x25519_peer_indexed_ladder
 // for the listed elements, and the shared inversion as a plain fe_invert (0 for 0, as k_batch_invert gives).  The contexts are copied
 // into a buffer of exactly n_ctx x 1600 bytes first, so that a build with -fsanitize=address sees a read past them.
-// Built into its own library by tests/test_host_emul_peer_ctx.py with the recipe of tests/host_emul/build.py.  Not part of the product.
+// Built into its own library by tests/test_host_emul_peer_ctx.py through tests/host_emul/build.py's build_lib.  Not part of the product.
 #define EMUL_COOP_WAVE_IMPL 1
 #include "coop_wave.h"
 #include "lanes.cuh"

@@ -8,7 +8,7 @@
 //   form 2  one element per two-wave workgroup: k_ed25519_sign_indexed_coop (the helper wave serving the SHA-512 schedules).
 // The contexts are copied into a buffer of exactly n_ctx x 128 bytes first, so that a build with -fsanitize=address sees a read past
 // them.  The base tables, the wide comb and the lock-step lane scheduler come from emul.cpp, included whole: this file is its own
-// library (tests/test_host_emul_sign_indexed.py, the recipe of tests/host_emul/build.py).  Not part of the product.
+// library (tests/test_host_emul_sign_indexed.py, through tests/host_emul/build.py's build_lib).  Not part of the product.
 #include "emul.cpp"
 #include "sign_ctx.cuh"
 

@@ -2,7 +2,7 @@
 // curve25519_amd/csrc/valu_gfx950.cuh plus stand-ins for the HIP keywords the device headers use, so that the
 // SAME device source (fe25519.cuh, sc25519.cuh, sha512.cuh, ge25519.cuh, x25519.cuh, lanes.cuh) can be compiled by
 // g++ and unit-tested on the CPU, one "lane" at a time, against Python big integers and the committed fixtures.
-// It is force-included (-include) by tests/host_emul/build.py only; nothing in the product links or includes it,
+// It is force-included (-include) by tests/host_emul/build.py's build_lib only; nothing in the product links or includes it,
 // and it is not a fallback: libcurve25519_amd.so has no host arithmetic at all.
 #pragma once
 #define C25519_VALU_PRIMITIVES 1

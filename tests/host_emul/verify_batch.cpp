@@ -4,7 +4,7 @@
 // kernels of engine_batch_eq.hip do across lanes -- the counting sort with atomics, the reductions -- is done here by plain host loops:
 //   emul_batcheq_digits   the signed digits of one scalar at width c (as an a_i or as a z_i); emul_batcheq_top_range: its top window's R;
 //   emul_batcheq          the whole chain for one call: enc(T) as the hook returns it, and the result.
-// Built into its own library by tests/test_host_emul_verify_batch.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_verify_batch.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #include "emul.cpp"
 #include "msm25519.cuh"

@@ -5,7 +5,7 @@
 // with atomics, the reductions -- is done here by plain host loops:
 //   emul_keyeq_fold   eight 64-bit word sums -> the key's scalar mod L, biased for width c (msm_key_fold), and whether it is non-zero;
 //   emul_keyeq        the whole chain for one call: enc(T) as the hook returns it, and the result.
-// Built into its own library by tests/test_host_emul_verify_batch_indexed.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_verify_batch_indexed.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #include "emul.cpp"
 #include "msm25519.cuh"

@@ -4,7 +4,7 @@
 // (csrc/batch_invert_lane.inc) over the products it left, in workgroups of 64 lock-step lanes; and the per-context rule 2
 // (zip215_ctx_key_ok).  The points come from the caller (tests/check_zip215_model.py computes T = [S]B - [k]A in big integers and
 // scales it by a Z of its choice), so the walk itself -- tests/host_emul/indexed_check.cpp's subject -- is not run again here.
-// Built into its own library by tests/test_host_emul_verify_check_zip215.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_verify_check_zip215.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #define EMUL_COOP_WAVE_IMPL 1
 #include "coop_wave.h"

@@ -8,7 +8,7 @@
 //   emul_strict_key         coop::strict_key_ok, the key check of k_ed25519_verify_check_strict_mask, by 64 lock-step lanes;
 //   emul_strict_waves       k_ed25519_verify_one_per_group_strict: coop::verify_three_waves<true> as 192 lock-step lanes, then the
 //                           reference order for the listed elements.
-// Built into its own library by tests/test_host_emul_verify_strict.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_verify_strict.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #include "emul.cpp"
 #include "strict25519.cuh"

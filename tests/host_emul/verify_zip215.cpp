@@ -9,7 +9,7 @@
 //   emul_zip215_waves    k_ed25519_verify_one_per_group_zip215: coop::verify_three_waves<false, true> as 192 lock-step lanes;
 //   emul_zip215_plain_strict   the plain and the strict lane chains' verdicts, for the property test on honest signatures.
 // listed[i] = 1 where the cofactored reference order decided the element, rejected[i] = 1 where it got verdict 0 without a walk.
-// Built into its own library by tests/test_host_emul_verify_zip215.py with the recipe of tests/host_emul/build.py.
+// Built into its own library by tests/test_host_emul_verify_zip215.py through tests/host_emul/build.py's build_lib.
 // Not part of the product.
 #include "emul.cpp"
 

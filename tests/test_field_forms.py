@@ -6,32 +6,22 @@ vectors of the reference (tests/golden/kat.json)."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import open_lib
 import vectors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.join(ROOT, "tests", "host_emul")
 KAT = json.load(open(os.path.join(ROOT, "tests", "golden", "kat.json")))
 
 
 @pytest.fixture(scope="module")
 def forms():
-    lib = os.path.join(HERE, "libc25519_forms.so")
-    srcs = [os.path.join(HERE, "forms.cpp"), os.path.join(HERE, "valu_model.h"),
-            os.path.join(ROOT, "tools", "ubench", "field_forms.cuh"), os.path.join(ROOT, "curve25519_amd", "csrc", "fe25519.cuh")]
-    if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
-                               "-Wno-unused-function", "-include", os.path.join(HERE, "valu_model.h"),
-                               "-I", os.path.join(ROOT, "curve25519_amd", "csrc"), "-I", os.path.join(ROOT, "tools", "ubench"),
-                               os.path.join(HERE, "forms.cpp"), "-o", lib])
-    L = C.CDLL(lib)
-    L.forms_fe_op.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
-    L.forms_x25519.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return L
+    return open_lib({"forms_fe_op": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int],
+                     "forms_x25519": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]},
+                    "forms.cpp", "libc25519_forms.so", extra_include_dirs=[os.path.join(ROOT, "tools", "ubench")], mad_counter=False)
 
 
 @pytest.mark.parametrize("form", [8, 9])

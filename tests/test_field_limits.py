@@ -13,21 +13,15 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tests", "host_emul"))
 import limb_vectors as lv  # noqa: E402
+from host_emul.build import assert_no_mad_overflow, open_lib  # noqa: E402
 
 SHAPES = {"lane": ("emul_fe_limb_op", lv.LANE_OPS, lv.lane_cases), "quad": ("emul_quad_limb_op", lv.QUAD_OPS, lv.quad_cases),
           "wave": ("emul_wave_limb_op", lv.WAVE_OPS, lv.wave_cases)}
 
 
 def load_model():
-    import build as emul_build
-    lib = C.CDLL(emul_build.build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    for name, _, _ in SHAPES.values():
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        getattr(lib, name).restype = None
-    return lib
+    return open_lib({name: ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], None) for name, _, _ in SHAPES.values()})
 
 
 @pytest.fixture(scope="module")
@@ -35,7 +29,7 @@ def model():
     lib = load_model()
     assert lib.emul_mad_overflow_count() == 0
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def run_model(lib, shape, op, recs):
@@ -108,7 +102,7 @@ def test_point_ops_agree_across_shapes(model):
 
 BITE = r"""
 import sys
-sys.path[:0] = [{tests!r}, {emul!r}]
+sys.path[:0] = [{tests!r}]
 import limb_vectors as lv, test_field_limits as t
 lib = t.load_model()
 recs = lv.lane_cases(0, scale=1.05)
@@ -121,7 +115,7 @@ def test_the_inputs_sit_at_the_edge():
     """Bite test: the same generator at 1.05 x the contract's maxima (fe_mul's b at beta 3.47, so 19 b wraps 32 bits) must produce
     wrong values on the model -- the cases above really are at the limit.  In a process of its own: the overflow it provokes must
     not count against the other tests."""
-    code = BITE.format(tests=os.path.join(ROOT, "tests"), emul=os.path.join(ROOT, "tests", "host_emul"))
+    code = BITE.format(tests=os.path.join(ROOT, "tests"))
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
     wrong, _ = map(int, p.stdout.split())

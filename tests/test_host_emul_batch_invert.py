@@ -3,27 +3,19 @@ kernel of every large batch).  The same source is compiled by g++ and run as wav
 the quads' quad_perm exchange as rendezvous), at every instantiated group size and at ragged sizes, with zeros placed on the slot
 map (tests/invert_cases.py) in every limb form the producers store.  Every 1 / z must equal z^(p-2) mod p, and 0 where z = 0."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import invert_cases as cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "host_emul"))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import build as emul_build
-    lib = C.CDLL(emul_build.build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_batch_invert.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    lib.emul_batch_invert.restype = C.c_int
+    lib = open_lib({"emul_batch_invert": ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], C.c_int)})
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def invert(lib, limbs, n, k):

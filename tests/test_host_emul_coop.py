@@ -8,15 +8,15 @@ do what the model says."""
 import ctypes as C
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from curve25519_amd import synth
+from host_emul.build import assert_no_mad_overflow, open_lib
+import vectors
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "host_emul"))
-from curve25519_amd import synth  # noqa: E402
-import vectors  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 KAT = json.load(open(os.path.join(GOLD, "kat.json")))
@@ -101,11 +101,7 @@ class Wave:
 
 @pytest.fixture(scope="module")
 def lib():
-    import build as emul_build
-    lib = C.CDLL(emul_build.build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_coop_sync_points.restype = C.c_ulonglong
-    for name, args in {"emul_coop_x25519": [vp, vp, vp, sz], "emul_coop_x25519_two_waves": [vp, vp, vp, sz],
+    lib = open_lib({name: (args, None) for name, args in {"emul_coop_x25519": [vp, vp, vp, sz], "emul_coop_x25519_two_waves": [vp, vp, vp, sz],
                        "emul_coop_public_fast": [vp, vp, sz, C.c_int],
                        "emul_coop_keypair": [vp, vp, vp, vp, sz, C.c_int], "emul_coop_sign": [vp, vp, vp, vp, sz, sz, C.c_int],
                        "emul_coop_blinding_init": [vp, vp, sz], "emul_coop_verify_init": [vp, vp, sz],
@@ -113,11 +109,10 @@ def lib():
                        "emul_coop_verify_three_waves": [vp, vp, vp, vp, vp, sz, sz, C.c_int],
                        "emul_blinding_init": [vp, vp, sz], "emul_ed25519_verify_init": [vp, vp, sz],
                        "emul_ed25519_verify": [vp, vp, vp, vp, vp, sz, sz],
-                       "emul_ed25519_verify_fast": [vp, vp, vp, vp, vp, sz, sz]}.items():
-        getattr(lib, name).argtypes = args
-        getattr(lib, name).restype = None
+                       "emul_ed25519_verify_fast": [vp, vp, vp, vp, vp, sz, sz]}.items()})
+    lib.emul_coop_sync_points.restype = C.c_ulonglong
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 @pytest.fixture(scope="module")

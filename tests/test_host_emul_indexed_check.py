@@ -1,50 +1,29 @@
 """CPU tests of ed25519_Verify_Check against many contexts in one call (curve25519_amd/csrc/verify_ctx.cuh: what
 ed25519_Verify_Check_indexed_* runs on the device).  The device source -- the per-lane kernel's index gather and walk over the
 context's rows, and the shared inversion's lanes with the index-aware finish -- is compiled by g++ against the C model of the gfx950
-primitives (tests/host_emul/indexed_check.cpp, the recipe of tests/host_emul/build.py) and judged element by element against the
+primitives (tests/host_emul/indexed_check.cpp, tests/host_emul/build.py's build_lib) and judged element by element against the
 oracle's orc_ed25519_verify_check on the same 2080-byte context (orc_sigv_ctx has Verify_Init's layout).  Contexts: honest ones as
 orc_ed25519_verify_init writes them and in canonical form, a flipped row byte, rows >= p, garbage keys, random bytes.  Signatures:
 valid, corrupted, and R = 32 zero bytes.  Indices n_ctx - 1, n_ctx and 0xffffffff: the last two must give 0, also where R is zero
 (the zero point a bad index leaves behind encodes to 32 zero bytes)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_indexed_check.so")
-SRCS = [os.path.join(HERE, f) for f in ("indexed_check.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, h) for h in ("verify_ctx.cuh", "batch_invert.cuh", "batch_invert_lane.inc", "ge25519.cuh", "fe25519.cuh",
-                                        "lanes.cuh", "sha512.cuh", "sc25519.cuh", "quad25519.cuh", "valu_gfx950.cuh",
-                                        "curve_constants.cuh")]
+from host_emul.build import assert_no_mad_overflow, open_lib
+
 P = 2**255 - 19
 CTX = 2080
 vp, sz = C.c_void_p, C.c_size_t
 
 
-def build() -> str:
-    srcs = [s for s in SRCS if os.path.exists(s)]
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in srcs):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "indexed_check.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_indexed_check.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_int, C.c_int]
-    lib.emul_indexed_check.restype = C.c_int
+    lib = open_lib({"emul_indexed_check": ([vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_int, C.c_int], C.c_int)},
+                   "indexed_check.cpp", "libc25519_emul_indexed_check.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 @pytest.fixture(scope="module")

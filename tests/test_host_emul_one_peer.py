@@ -1,52 +1,29 @@
 """CPU tests of X25519 against ONE peer key over the peer's wide comb (curve25519_amd/csrc/x25519_peer.cuh: what
 curve25519_dh_CreateSharedKey_one_peer_* runs on the device).  The device source is compiled by g++ against the C model of the
-gfx950 primitives (tests/host_emul/one_peer.cpp, the recipe of tests/host_emul/build.py) and judged against a Python
+gfx950 primitives (tests/host_emul/one_peer.cpp, tests/host_emul/build.py's build_lib) and judged against a Python
 big-integer ladder that reads u unmasked, and against the reference's own curve25519_dh_CreateSharedKey where it is built.
 Every peer class: the known-answer keys, the small-order u, the twist and u = -1 (which must be refused), keys with bit 255
 set, public keys of random secrets and random byte strings -- about half of the latter land on the curve WITH a torsion
 component, the case the k >> 3 / 8P identity exists for."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import one_peer_cases as cases
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_one_peer.so")
-SRCS = [os.path.join(HERE, f) for f in ("one_peer.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, h) for h in ("x25519_peer.cuh", "ge25519.cuh", "fe25519.cuh", "x25519.cuh", "lanes.cuh", "valu_gfx950.cuh",
-                                        "safegcd25519.cuh", "curve_constants.cuh")]
 vp, sz = C.c_void_p, C.c_size_t
 SECRETS = 4                            # per peer
 
 
-def build() -> str:
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in SRCS):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "one_peer.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_one_peer.argtypes = [vp, vp, vp, sz]
-    lib.emul_one_peer.restype = C.c_int
-    lib.emul_one_peer_point.argtypes = [vp, vp]
-    lib.emul_one_peer_point.restype = C.c_int
-    lib.emul_one_peer_rows.argtypes = [vp, vp, vp, sz]
-    lib.emul_one_peer_rows.restype = None
+    lib = open_lib({"emul_one_peer": ([vp, vp, vp, sz], C.c_int), "emul_one_peer_point": ([vp, vp], C.c_int),
+                    "emul_one_peer_rows": ([vp, vp, vp, sz], None)},
+                   "one_peer.cpp", "libc25519_emul_one_peer.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def secrets(seed, n=SECRETS):

@@ -1,51 +1,28 @@
 """CPU tests of X25519 against many peer contexts (curve25519_amd/csrc/x25519_peer_ctx.cuh: what curve25519_dh_Peer_Init_* and
 curve25519_dh_CreateSharedKey_indexed_* run on the device).  The device source is compiled by g++ against the C model of the gfx950
-primitives (tests/host_emul/peer_ctx.cpp, the recipe of tests/host_emul/build.py).  The context bytes are judged against the Python
+primitives (tests/host_emul/peer_ctx.cpp, tests/host_emul/build.py's build_lib).  The context bytes are judged against the Python
 big-integer model of the layout (tests/peer_ctx_model.py), the shared keys against the big-integer ladder of tests/one_peer_cases.py
 and the reference's own curve25519_dh_CreateSharedKey where it is built.  Every peer class: KAT keys, small order, twist, u = -1,
 bit 255 set, public keys of random secrets and random byte strings (some on the curve with a torsion component)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import one_peer_cases as cases
 import peer_ctx_model as model
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_peer_ctx.so")
-SRCS = [os.path.join(HERE, f) for f in ("peer_ctx.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, h) for h in ("x25519_peer_ctx.cuh", "x25519_peer.cuh", "ge25519.cuh", "fe25519.cuh", "x25519.cuh", "lanes.cuh",
-                                        "valu_gfx950.cuh", "safegcd25519.cuh", "curve_constants.cuh")]
 vp, sz = C.c_void_p, C.c_size_t
-
-
-def build() -> str:
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in SRCS):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "peer_ctx.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_peer_init.argtypes = [vp, vp, sz]
-    lib.emul_peer_init.restype = None
-    lib.emul_peer_indexed.argtypes = [vp, vp, sz, vp, vp, sz]
-    lib.emul_peer_indexed.restype = C.c_long
-    lib.emul_peer_gather.argtypes = [vp, vp, sz, vp, sz]
-    lib.emul_peer_gather.restype = None
+    lib = open_lib({"emul_peer_init": ([vp, vp, sz], None), "emul_peer_indexed": ([vp, vp, sz, vp, vp, sz], C.c_long),
+                    "emul_peer_gather": ([vp, vp, sz, vp, sz], None)},
+                   "peer_ctx.cpp", "libc25519_emul_peer_ctx.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def peer_init(lib, pks):

@@ -5,13 +5,13 @@ fixtures (the real reference's outputs).  What the GPU suite adds is that the ha
 import ctypes as C
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "host_emul"))
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 KAT = json.load(open(os.path.join(GOLD, "kat.json")))
@@ -29,17 +29,13 @@ def ptr(a):
 
 @pytest.fixture(scope="module")
 def lib():
-    import build as emul_build
-    lib = C.CDLL(emul_build.build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_coop_sync_points.restype = C.c_ulonglong
-    for name, args in {"emul_quad_x25519": [vp, vp, vp, sz], "emul_quad_verify": [vp, vp, vp, vp, vp, sz, sz],
+    lib = open_lib({name: (args, None) for name, args in {"emul_quad_x25519": [vp, vp, vp, sz],
+                       "emul_quad_verify": [vp, vp, vp, vp, vp, sz, sz],
                        "emul_quad_keypair": [vp, vp, vp, sz], "emul_quad_sign": [vp, vp, vp, sz, sz], "emul_quad_public_fast": [vp, vp, sz],
-                       "emul_ed25519_verify_fast": [vp, vp, vp, vp, vp, sz, sz]}.items():
-        getattr(lib, name).argtypes = args
-        getattr(lib, name).restype = None
+                       "emul_ed25519_verify_fast": [vp, vp, vp, vp, vp, sz, sz]}.items()})
+    lib.emul_coop_sync_points.restype = C.c_ulonglong
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def quad_x25519(lib, pk, sk):

@@ -7,49 +7,26 @@ model of tests/sign_ctx_model.py for contexts that no private key gives (random 
 sides of each SHA-512 block edge of the two prefixed hashes (H(prefix || m): 32 + len + 17 bytes; H(enc(R) || pk || m): 64 + len +
 17).  Indices n_ctx and 0xffffffff give 64 zero bytes."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import sign_ctx_model as model
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_sign_ctx.so")
-SRCS = [os.path.join(HERE, f) for f in ("sign_ctx.cpp", "emul.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, h) for h in ("sign_ctx.cuh", "lanes.cuh", "sha512.cuh", "sc25519.cuh", "ge25519.cuh", "fe25519.cuh",
-                                        "coop25519.cuh", "coop_ops.cuh", "quad25519.cuh", "verify_fast.cuh", "batch_invert.cuh",
-                                        "valu_gfx950.cuh", "curve_constants.cuh", "x25519.cuh")]
 CTX = 128
 FORMS = [(0, 0, "lane/lds-comb"), (0, 1, "lane/wide"), (1, 1, "quad"), (2, 0, "wave/lds-comb"), (2, 1, "wave/wide")]
 EDGE_LENGTHS = [0, 47, 48, 79, 80, 175, 176, 207, 208, 1000]
 vp, sz = C.c_void_p, C.c_size_t
 
 
-def build() -> str:
-    srcs = [s for s in SRCS if os.path.exists(s)]
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in srcs):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "sign_ctx.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_sign_ctx_init.argtypes = [vp, vp, sz]
-    lib.emul_sign_ctx_init.restype = None
-    lib.emul_sign_indexed.argtypes = [vp, vp, sz, vp, vp, sz, vp, sz, C.c_int, C.c_int]
-    lib.emul_sign_indexed.restype = None
+    lib = open_lib({"emul_sign_ctx_init": ([vp, vp, sz], None),
+                    "emul_sign_indexed": ([vp, vp, sz, vp, vp, sz, vp, sz, C.c_int, C.c_int], None)},
+                   "sign_ctx.cpp", "libc25519_emul_sign_ctx.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def keys(orc, k, seed):

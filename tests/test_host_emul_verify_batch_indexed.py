@@ -1,50 +1,31 @@
 """CPU tests of the ZIP-215 batch equation with coalesced keys (what ed25519_VerifyBatch_zip215_indexed_* runs on the device from
 BATCH_EQ_INDEXED_MIN).  The lane-level device source, curve25519_amd/csrc/msm25519.cuh, is compiled by g++ against the C model of the
-gfx950 primitives (tests/host_emul/verify_batch_indexed.cpp, the recipe of tests/host_emul/build.py); a host counting sort and host
+gfx950 primitives (tests/host_emul/verify_batch_indexed.cpp, tests/host_emul/build.py's build_lib); a host counting sort and host
 accumulation stand in for the kernels' atomics.  Expected points and results: the rule in Python big integers
 (tests/batch_eq_indexed_model.py), and the un-indexed rule on the gathered keys (tests/batch_eq_model.py) for the result."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import batch_eq_indexed_model as im
 import batch_eq_model as bm
 import zip215_cases as zc
 from vectors import L
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_verify_batch_indexed.so")
-SRCS = [os.path.join(HERE, f) for f in ("verify_batch_indexed.cpp", "emul.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cuh", ".inc"))]
 vp, sz = C.c_void_p, C.c_size_t
 WIDTHS = (8, 10, 13)
 SEEDS = [bytes([19 * j + 5]) * 32 for j in range(8)]
 
 
-def build() -> str:
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in SRCS):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE,
-                           os.path.join(HERE, "verify_batch_indexed.cpp"), "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_keyeq_fold.argtypes = [vp, vp, C.c_int]
-    lib.emul_keyeq.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, C.c_int]
+    lib = open_lib({"emul_keyeq_fold": [vp, vp, C.c_int], "emul_keyeq": [vp, vp, sz, vp, vp, vp, sz, sz, vp, C.c_int]},
+                   "verify_batch_indexed.cpp", "libc25519_emul_verify_batch_indexed.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def ptr(a):

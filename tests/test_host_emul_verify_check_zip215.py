@@ -1,53 +1,31 @@
 """CPU tests of the coset comparison behind ed25519_Verify_Check_zip215_* (curve25519_amd/csrc/verify_ctx_zip215.cuh).  The device
 source -- the coset prep's lane, the shared inversion's lanes with FinishVerifyZip215, the per-context rule 2 -- is compiled by g++
-against the C model of the gfx950 primitives (tests/host_emul/verify_check_zip215.cpp, the recipe of tests/host_emul/build.py) and
+against the C model of the gfx950 primitives (tests/host_emul/verify_check_zip215.cpp, tests/host_emul/build.py's build_lib) and
 judged element by element against tests/check_zip215_model.py, which supplies T = [S]B - [k]A in big integers, scaled by a Z != 1
 of its choice.  Sets: ZIP-215's conformance grid, the torsion and degenerate sets, the generated torsion-shift set."""
 import ctypes as C
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import CSRC, assert_no_mad_overflow, open_lib
 import check_zip215_model as cm
 import zip215_cases as zc
 from vectors import P, small_order_encodings
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_verify_check_zip215.so")
-SRCS = [os.path.join(HERE, f) for f in ("verify_check_zip215.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, h) for h in ("verify_ctx_zip215.cuh", "verify_ctx.cuh", "strict25519.cuh", "batch_invert.cuh",
-                                        "batch_invert_lane.inc", "ge25519.cuh", "fe25519.cuh", "lanes.cuh", "sha512.cuh", "sc25519.cuh",
-                                        "quad25519.cuh", "valu_gfx950.cuh", "curve_constants.cuh")]
 vp, sz = C.c_void_p, C.c_size_t
-
-
-def build() -> str:
-    srcs = [s for s in SRCS if os.path.exists(s)]
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in srcs):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE,
-                           os.path.join(HERE, "verify_check_zip215.cpp"), "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_zip215_ctx_key_ok.argtypes = [vp]
-    lib.emul_zip215_ctx_key_ok.restype = C.c_uint
-    lib.emul_check_zip215_finish.argtypes = [vp, vp, vp, sz, vp, vp, sz, C.c_int]
-    lib.emul_check_zip215_finish.restype = C.c_int
+    lib = open_lib({"emul_zip215_ctx_key_ok": ([vp], C.c_uint),
+                    "emul_check_zip215_finish": ([vp, vp, vp, sz, vp, vp, sz, C.c_int], C.c_int)},
+                   "verify_check_zip215.cpp", "libc25519_emul_verify_check_zip215.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def points_for(sig, pk, msg, seed):

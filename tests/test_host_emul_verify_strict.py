@@ -1,48 +1,29 @@
 """CPU tests of the strict verification (curve25519_amd/csrc/strict25519.cuh and the Strict branches of the lattice path: what
 ed25519_VerifySignature_strict_* runs on the device).  The device source is compiled by g++ against the C model of the gfx950
-primitives (tests/host_emul/verify_strict.cpp, the recipe of tests/host_emul/build.py): the predicates on raw values, the lane chain
+primitives (tests/host_emul/verify_strict.cpp, tests/host_emul/build.py's build_lib): the predicates on raw values, the lane chain
 and the per-wave code as 192 lock-step lanes.  Expected verdicts: the strict rule in Python big integers (tests/strict_cases.py) on
 top of the reference's verdict (the oracle's, or tests/golden/degenerate_verify.npz's)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import strict_cases as sc
 from vectors import L, P
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_verify_strict.so")
-SRCS = [os.path.join(HERE, f) for f in ("verify_strict.cpp", "emul.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cuh", ".inc"))]
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 vp, sz = C.c_void_p, C.c_size_t
-
-
-def build() -> str:
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in SRCS):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "verify_strict.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_strict_predicates.argtypes = [vp, vp, sz]
-    lib.emul_strict_key.argtypes = [vp, vp, sz]
-    for f in (lib.emul_strict_lane, lib.emul_strict_waves):
-        f.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, C.c_int]
-        f.restype = None
+    lib = open_lib({"emul_strict_predicates": [vp, vp, sz], "emul_strict_key": [vp, vp, sz],
+                    **{f: ([vp, vp, vp, vp, vp, vp, sz, sz, C.c_int], None) for f in ("emul_strict_lane", "emul_strict_waves")}},
+                   "verify_strict.cpp", "libc25519_emul_verify_strict.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def ptr(a):
@@ -105,7 +86,7 @@ def test_lane_chain_over_long_vectors_keep_strict_verdicts(lib, edges):
 
 
 def test_degenerate_golden_lane(lib):
-    g = np.load(os.path.join(os.path.dirname(HERE), "golden", "degenerate_verify.npz"))
+    g = np.load(os.path.join(GOLD, "degenerate_verify.npz"))
     want = sc.strict_rule(g["sig"], g["pk"], g["verdict"])
     assert g["verdict"].sum() > want.sum()                                       # the set is where the two semantics differ
     ok, listed, rej = run(lib, "lane", g["sig"], g["pk"], g["msg"])
@@ -144,7 +125,7 @@ def test_three_waves_equal_the_rule(lib, edges):
 
 
 def test_three_waves_degenerate_golden(lib):
-    g = np.load(os.path.join(os.path.dirname(HERE), "golden", "degenerate_verify.npz"))
+    g = np.load(os.path.join(GOLD, "degenerate_verify.npz"))
     idx = np.concatenate([np.nonzero(g["verdict"] == 1)[0][::4], np.nonzero(g["label"] >= 3)[0][::5]])
     want = sc.strict_rule(g["sig"][idx], g["pk"][idx], g["verdict"][idx])
     ok, listed, rej = run(lib, "waves", g["sig"][idx], g["pk"][idx], g["msg"][idx])

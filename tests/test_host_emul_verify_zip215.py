@@ -1,48 +1,27 @@
 """CPU tests of the ZIP-215 verification (what ed25519_VerifySignature_zip215_* runs on the device).  The device source is compiled by
-g++ against the C model of the gfx950 primitives (tests/host_emul/verify_zip215.cpp, the recipe of tests/host_emul/build.py): the
+g++ against the C model of the gfx950 primitives (tests/host_emul/verify_zip215.cpp, tests/host_emul/build.py's build_lib): the
 decoding, the lane chain, the quad walk and the per-wave code as lock-step lanes, and the cofactored reference-order fallback.
 Expected verdicts: the rule in Python big integers (tests/zip215_cases.py), whose own properties are asserted first."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_emul.build import assert_no_mad_overflow, open_lib
 import zip215_cases as zc
 from vectors import L, P
 
-HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "host_emul")
-CSRC = os.path.join(os.path.dirname(HERE), "..", "curve25519_amd", "csrc")
-LIB = os.path.join(HERE, "libc25519_emul_verify_zip215.so")
-SRCS = [os.path.join(HERE, f) for f in ("verify_zip215.cpp", "emul.cpp", "valu_model.h", "coop_wave.h")] + \
-       [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cuh", ".inc"))]
 vp, sz = C.c_void_p, C.c_size_t
 SHAPES = ("lane", "quad", "waves")
 
 
-def build() -> str:
-    if os.path.exists(LIB) and all(os.path.getmtime(s) <= os.path.getmtime(LIB) for s in SRCS):
-        return LIB
-    tmp = f"{LIB}.tmp.{os.getpid()}"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                           "-include", os.path.join(HERE, "valu_model.h"), "-I", CSRC, "-I", HERE, os.path.join(HERE, "verify_zip215.cpp"),
-                           "-o", tmp, "-lpthread"])
-    os.replace(tmp, LIB)
-    return LIB
-
-
 @pytest.fixture(scope="module")
 def lib():
-    lib = C.CDLL(build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
-    lib.emul_zip215_decode.argtypes = [vp, vp, vp, sz]
-    lib.emul_zip215_plain_strict.argtypes = [vp, vp, vp, vp, vp, sz, sz]
-    for f in (lib.emul_zip215_lane, lib.emul_zip215_quad, lib.emul_zip215_waves):
-        f.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, C.c_int]
-        f.restype = None
+    lib = open_lib({"emul_zip215_decode": [vp, vp, vp, sz], "emul_zip215_plain_strict": [vp, vp, vp, vp, vp, sz, sz],
+                    **{"emul_zip215_" + s: ([vp, vp, vp, vp, vp, vp, sz, sz, C.c_int], None) for s in SHAPES}},
+                   "verify_zip215.cpp", "libc25519_emul_verify_zip215.so")
     yield lib
-    assert lib.emul_mad_overflow_count() == 0, "a v_mad_u64_u32 column wrapped 2^64: the bound contract is broken"
+    assert_no_mad_overflow(lib)
 
 
 def ptr(a):

@@ -2,22 +2,7 @@
 cross-compiled for gfx950 -- no GPU needed).  A spill in one of these kernels does not fail any parity test, it just
 costs time on the device; round 2 shipped with several that nobody had asked the compiler about.  The same
 parse prints profiles/rNN_resource_usage.txt (tools/resource_usage.py)."""
-import os
-import shutil
-import sys
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
+from kernel_usage import resource_usage, usage  # noqa: F401
 
 
 # kernel (demangled prefix) -> the most registers it may allocate per lane (VGPR + AGPR): what its occupancy target allows
@@ -56,3 +41,8 @@ def test_every_kernel_is_spill_free(usage):
     """... and nothing else in the library spills either (self-test hooks, table generation, the rare slow path)."""
     bad = {n: k["scratch"] for n, k in usage.items() if k.get("scratch", 0)}
     assert not bad, bad
+
+
+def test_the_engine_is_compiled_once_per_process(usage):
+    """every tests/test_resources*.py module takes `usage`; alone or with the other eight, one run of the compiler serves them all"""
+    assert resource_usage.compiles == 1

@@ -1,25 +1,6 @@
 """Register / scratch budgets of the kernels behind ed25519_Verify_Check_indexed_* (many contexts in one call), from the compiler's
-own remarks (tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
-import os
-import shutil
-import sys
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
-
-
-def regs(k):
-    return k["vgpr"] + k.get("agpr", 0)
+own remarks (tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
+from kernel_usage import regs, usage  # noqa: F401
 
 
 def test_per_lane_kernel_fits_two_waves_per_simd(usage):

@@ -1,26 +1,7 @@
 """Register / scratch budgets of the kernels behind curve25519_dh_Peer_Init_* and curve25519_dh_CreateSharedKey_indexed_* (many peer
-contexts in one call), from the compiler's own remarks (tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage,
+contexts in one call), from the compiler's own remarks (tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage,
 cross-compiled for gfx950)."""
-import os
-import shutil
-import sys
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
-
-
-def regs(k):
-    return k["vgpr"] + k.get("agpr", 0)
+from kernel_usage import regs, usage  # noqa: F401
 
 
 def test_walk_fits_four_waves_per_simd(usage):

@@ -1,15 +1,10 @@
 """Register / scratch budgets of the kernels behind ed25519_Sign_Init_* and ed25519_SignMessage_indexed_* (many signer contexts in one
-call), from the compiler's own remarks (tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage,
+call), from the compiler's own remarks (tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage,
 cross-compiled for gfx950).  Each indexed kernel is held to the occupancy its launch bounds ask for and to the registers of the
 ed25519_SignMessage kernel it mirrors."""
-import os
-import shutil
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from kernel_usage import regs, usage  # noqa: F401
 
 # new kernel -> (register budget of its launch bounds, the ed25519_SignMessage kernel it mirrors)
 KERNELS = {
@@ -20,18 +15,6 @@ KERNELS = {
     "k_ed25519_sign_indexed_coop<true>": (168, "k_ed25519_sign_coop<true>"),               # two waves per workgroup, three per SIMD
     "k_ed25519_sign_indexed_coop<false>": (168, "k_ed25519_sign_coop<false>"),
 }
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
-
-
-def regs(k):
-    return k["vgpr"] + k.get("agpr", 0)
 
 
 @pytest.mark.parametrize("name", sorted(KERNELS))

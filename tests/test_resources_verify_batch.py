@@ -1,23 +1,10 @@
 """Register / scratch budgets of the ZIP-215 batch equation's kernels (csrc/engine_batch_eq.hip), from the compiler's own remarks
-(tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
-import os
-import shutil
-import sys
-
+(tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from kernel_usage import usage  # noqa: F401
 
 KERNELS = ["points", "scalars", "count", "scan", "scatter", "buckets", "windows", "tail", "and"]
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
 
 
 def test_the_equation_has_its_kernels_and_none_is_a_zip215_twin(usage):

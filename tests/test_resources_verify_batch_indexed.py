@@ -1,24 +1,11 @@
 """Register / scratch budgets of the coalesced ZIP-215 batch equation's own kernels (k_ed25519_keyeq_* in csrc/engine_batch_eq.hip; the
 scan, the buckets, the windows and the tail are the plain equation's: tests/test_resources_verify_batch.py), from the compiler's own
-remarks (tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
-import os
-import shutil
-import sys
-
+remarks (tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from kernel_usage import usage  # noqa: F401
 
 KERNELS = ["points", "scalars", "fold", "count", "scatter", "gather"]
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
 
 
 def test_the_coalesced_equation_has_its_kernels_under_their_own_name(usage):

@@ -1,28 +1,11 @@
 """Register / scratch budgets of the kernels ed25519_Verify_Check_zip215_* adds, from the compiler's own remarks
-(tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950): every one spill-free."""
-import os
-import shutil
-import sys
-
+(tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950): every one spill-free."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from kernel_usage import spill_free, usage  # noqa: F401
 
 PLAIN = ["k_ed25519_verify_coset_prep", "k_ed25519_verify_coset_key_gather", "k_ed25519_verify_coset_index_mask"]
 GROUPS = [12, 8, 4, 2, 1]          # launch_coset_finish (engine_verify.hip): this finish is instantiated up to 12 elements per lane
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
-
-
-def spill_free(k):
-    return k.get("scratch", 0) == 0 and k.get("vgpr_spill", 0) == 0 and k.get("sgpr_spill", 0) == 0
 
 
 @pytest.mark.parametrize("name", PLAIN)

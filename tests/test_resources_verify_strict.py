@@ -1,28 +1,11 @@
 """Register / scratch budgets of the strict verification kernels against their plain twins, from the compiler's own remarks
-(tools/resource_usage.compile_remarks: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
-import os
-import shutil
-import sys
-
+(tools/resource_usage.kernel_usage: hipcc -Rpass-analysis=kernel-resource-usage, cross-compiled for gfx950)."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from kernel_usage import regs, usage  # noqa: F401
 
 TWINS = ["k_ed25519_verify_fast_scalars", "k_ed25519_verify_fast_points", "k_ed25519_verify_quad_prep", "k_ed25519_verify_quad_walk",
          "k_ed25519_verify_one_per_group"]
-
-
-@pytest.fixture(scope="module")
-def usage():
-    if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
-        pytest.skip("hipcc not available")
-    import resource_usage
-    return {k["pretty"]: k for k in resource_usage.compile_remarks()}
-
-
-def regs(k):
-    return k["vgpr"] + k.get("agpr", 0)
 
 
 def waves(k):

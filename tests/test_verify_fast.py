@@ -5,24 +5,22 @@ signatures, S >= L, garbage keys (off-curve ones must ask for the reference-orde
 produces, keys and R's with torsion components (where a cofactored check would differ), small-order keys."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
+from curve25519_amd import synth
+from host_emul.build import assert_no_mad_overflow, open_lib
+import vectors
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "host_emul"))
-from curve25519_amd import synth  # noqa: E402
-import vectors  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def emul():
-    import build as emul_build
-    lib = C.CDLL(emul_build.build())
-    lib.emul_mad_overflow_count.restype = C.c_ulonglong
+    lib = open_lib()
     yield lib
-    assert lib.emul_mad_overflow_count() == 0
+    assert_no_mad_overflow(lib)
 
 
 def run_fast(lib, sig, pk, msg):

@@ -7,8 +7,10 @@ Compiles curve25519_amd/csrc/engine.hip for gfx950 (device code only, nothing is
 -Rpass-analysis=kernel-resource-usage and prints one line per kernel.  `alloc` is the hardware allocation
 (VGPR + AGPR rounded up to the granule of 8), `waves` what the register file allows per SIMD (512 / alloc, at
 most 8); the launch bounds and LDS may lower it further (the compiler's own `Occupancy` column has those in).
-tests/test_resources.py asserts on the same parse (scratch = 0 for the hot kernels).
+tests/test_resources*.py assert on the same parse (scratch = 0 for the hot kernels) through kernel_usage(); the engine is compiled
+once per process however many modules ask.
 """
+import functools
 import os
 import re
 import shutil
@@ -53,14 +55,41 @@ def parse_remarks(text):
     return kernels
 
 
-def compile_remarks(extra_flags=()):
+compiles = 0          # how many times this process has run the compiler
+
+
+@functools.lru_cache(maxsize=None)
+def _remarks(flags):
+    global compiles
+    compiles += 1
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, *BUILD_FLAGS, *extra_flags, "--cuda-device-only", "-c", ENGINE, "-o", os.devnull,
+    cmd = [hipcc, *BUILD_FLAGS, *flags, "--cuda-device-only", "-c", ENGINE, "-o", os.devnull,
            "-Rpass-analysis=kernel-resource-usage"]
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + p.stderr[-4000:])
     return parse_remarks(p.stderr)
+
+
+def compile_remarks(extra_flags=()):
+    """-> the kernels' records.  One compile per process for each set of flags, whoever asks and however often; extra flags get a
+    compile of their own.  The records are shared: read them, do not change them."""
+    return _remarks(tuple(extra_flags))
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_usage():
+    """-> {pretty name: record} of the default build"""
+    return {k["pretty"]: k for k in compile_remarks()}
+
+
+def regs(k):
+    """registers allocated per lane: VGPR + AGPR"""
+    return k["vgpr"] + k.get("agpr", 0)
+
+
+def spill_free(k):
+    return k.get("scratch", 0) == 0 and k.get("vgpr_spill", 0) == 0 and k.get("sgpr_spill", 0) == 0
 
 
 def table(kernels):
