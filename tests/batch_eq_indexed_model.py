@@ -11,13 +11,17 @@ from vectors import ED_B, L
 from zip215_cases import zip215_decode
 
 
-def key_sums(keys, idx, sig, msg, seed):
+def _challenges(seed, n, index):
+    return bm.challenges(seed, n) if index is None else [bm.challenge(bytes(seed), int(i)) for i in index]
+
+
+def key_sums(keys, idx, sig, msg, seed, index=None):
     """(sums, s_sum, left_out): sums[j] = the integer sum of a_i = z_i k_i mod L over the elements that name key j and stay in the
-    equation; s_sum = sum z_i S_i mod L over them; left_out[i]: element i is rejected (S >= L, an R or a named key that does not decode,
-    an index out of range)"""
+    equation ({j: sum}, only the keys with such an element); s_sum = sum z_i S_i mod L over them; left_out[i]: element i is rejected
+    (S >= L, an R or a named key that does not decode, an index out of range).  index: as in batch_point"""
     n, n_key = len(sig), len(keys)
-    z = bm.challenges(seed, n)
-    sums, s_sum, left_out = [0] * n_key, 0, [False] * n
+    z = _challenges(seed, n, index)
+    sums, s_sum, left_out = {}, 0, [False] * n
     decoded = {}
     for i in range(n):
         j, sg, m = int(idx[i]), bytes(sig[i]), bytes(msg[i])
@@ -28,21 +32,28 @@ def key_sums(keys, idx, sig, msg, seed):
             left_out[i] = True
             continue
         k = int.from_bytes(hashlib.sha512(sg[:32] + bytes(keys[j]) + m).digest(), "little") % L
-        sums[j] += z[i] * k % L
+        sums[j] = sums.get(j, 0) + z[i] * k % L
         s_sum = (s_sum + z[i] * S) % L
     return sums, s_sum, left_out
 
 
-def batch_point(keys, idx, sig, msg, seed):
+def batch_point(keys, idx, sig, msg, seed, index=None):
     """(T, ok): the coalesced point in affine coordinates over the elements that stay, ok = every element stayed.  A key that no
-    remaining element names is never decoded."""
-    sums, s_sum, left_out = key_sums(keys, idx, sig, msg, seed)
-    z = bm.challenges(seed, len(sig))
+    remaining element names is never decoded.  index: the elements' own indices in the call (default 0 .. n - 1): the rows are then a
+    subset of a batch, and T is that subset's share of the batch's point provided no row outside the subset names one of its keys.
+    The elements that share one R (byte for byte) are taken together, [sum z_i]R with the sum as an integer: the same point whatever
+    R's order."""
+    sums, s_sum, left_out = key_sums(keys, idx, sig, msg, seed, index)
+    z = _challenges(seed, len(sig), index)
     acc = bm._mul(s_sum, bm._ext(ED_B))
+    z_of_r = {}
     for i in range(len(sig)):
         if not left_out[i]:
-            acc = bm._add(acc, bm._neg(bm._mul(z[i], bm._ext(zip215_decode(bytes(sig[i][:32]))))))
-    for j, total in enumerate(sums):
+            r = bytes(sig[i][:32])
+            z_of_r[r] = z_of_r.get(r, 0) + z[i]
+    for r, total in z_of_r.items():
+        acc = bm._add(acc, bm._neg(bm._mul(total, bm._ext(zip215_decode(r)))))
+    for j, total in sums.items():
         if total % L:
             acc = bm._add(acc, bm._neg(bm._mul(total % L, bm._ext(zip215_decode(bytes(keys[j]))))))
     return bm._affine(acc), not any(left_out)

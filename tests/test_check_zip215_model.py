@@ -1,10 +1,13 @@
 """The coset comparison of ed25519_Verify_Check_zip215_* (tests/check_zip215_model.py: no decoding of R) against the ZIP-215 rule as
 stated (tests/zip215_cases.py: decode R, multiply by 8): the conformance grid, the torsion and degenerate sets and a generated set of
-torsion-shifted R's in every encoding.  Big integers only."""
+torsion-shifted R's in every encoding; and the closed form of the batch equation's point (tests/batch_eq_model.py: rows whose S is
+moved by a known delta) against the slow models of the plain and the coalesced equation.  Big integers only."""
 import random
 
 import numpy as np
 
+import batch_eq_indexed_model as im
+import batch_eq_model as bm
 import check_zip215_model as cm
 import zip215_cases as zc
 from vectors import D_ED, P, ed_add, ed_mul
@@ -93,3 +96,54 @@ def test_zero_product_and_rule_2():
     assert cm.key_on_curve_from_row1((A[1] + nx) % P, (A[1] - nx) % P, A[1]) == 1
     assert cm.key_on_curve_from_row1((A[1] + nx + 1) % P, (A[1] - nx) % P, A[1]) == 0
     assert cm.key_on_curve_from_row1((A[1] + nx) % P, (A[1] - nx) % P, (A[1] + 1) % P) == 0
+
+
+# ---- the batch equation's closed form against its slow models ---------------------------------------------------------------
+
+def _shifted_dozen(oracle):
+    """12 rows: 9 honest ones (exactly valid, cofactorless) with S moved, one of them then rejected, and 3 torsion rows under one
+    mixed-order key at rows 2, 5, 11: (sig, pk, msg, special rows, shifted rows that stay, their deltas)"""
+    pub, priv = oracle.ed25519_keypair(oracle.random_bytes((12, 32), 0xC105ED))
+    msg = oracle.random_bytes((12, 32), 0xC105EE)
+    sig = oracle.ed25519_sign(priv, msg).copy()
+    assert oracle.ed25519_verify(sig, pub, msg).all()
+    tsig, tpk, tmsg = zc.torsion()
+    special = [2, 5, 11]
+    sig[special], pub[special], msg[special] = tsig[:3], tpk[:3], tmsg[:3]
+    assert len({bytes(k) for k in tpk[:3]}) == 1
+    rows = [i for i in range(12) if i not in special]
+    deltas = bm.odd_deltas(len(rows), 0xC105EF)
+    sig = bm.shift_s(sig, rows, deltas)
+    sig[7, 32:] = np.frombuffer(bm.L.to_bytes(32, "little"), np.uint8)            # S = L: the row drops out, its delta with it
+    kept = [(r, d) for r, d in zip(rows, deltas) if r != 7]
+    return sig, pub, msg, special, [r for r, _ in kept], [d for _, d in kept]
+
+
+def test_closed_form_of_the_batch_point_equals_the_slow_model(oracle):
+    sig, pk, msg, special, rows, deltas = _shifted_dozen(oracle)
+    seed = bytes(range(32))
+    sums = bm.shift_sums(seed, rows, deltas)
+    share = bm.subset_points(sig[special], pk[special], msg[special], seed, special, (3, 6, 12))
+    for n in (3, 6, 12):
+        want, ok = bm.batch_point(sig[:n], pk[:n], msg[:n], seed)
+        assert ok == (n <= 7) and bm.shifted_point(sums, n, share[n]) == want, n
+    assert bm._affine(share[12]) == bm.batch_point(sig[special], pk[special], msg[special], seed, index=special)[0]
+    # steering: row 9's delta replaced, then row 5's (a special row) moved as well -- the sum is zero, T the special rows' share
+    for j in (9, 5):
+        d = bm.steering_delta(seed, sums, 12, j)
+        base = sig if j in special else bm.shift_s(sig, [j], [-deltas[rows.index(j)]])
+        steered = bm.shift_s(base, [j], [d])
+        want, _ = bm.batch_point(steered, pk, msg, seed)
+        assert want == bm._affine(share[12]) and bm._affine(bm._mul(8, bm._ext(want))) == (0, 1), j
+        assert zc.zip215_rule(steered[[0, j]], pk[[0, j]], msg[[0, j]]).tolist() == [0, 0]
+
+
+def test_closed_form_of_the_coalesced_point_equals_the_slow_model(oracle):
+    sig, pk, msg, special, rows, deltas = _shifted_dozen(oracle)
+    seed = bytes(range(32, 64))
+    keys, idx = im.distinct_keys(pk)
+    assert len(keys) == 10
+    sp = np.array(special)
+    share, _ = im.batch_point(keys, idx[sp], sig[sp], msg[sp], seed, index=sp)
+    want, ok = im.batch_point(keys, idx, sig, msg, seed)
+    assert not ok and bm.shifted_point(bm.shift_sums(seed, rows, deltas), 12, bm._ext(share)) == want

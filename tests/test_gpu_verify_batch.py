@@ -1,7 +1,9 @@
 """GPU suite (MI355X): ZIP-215 batch verification, one equation per call -- ed25519_VerifyBatch_zip215_batch / _dev / _ragged_batch /
 _ragged_dev and the hook c25519_amd_verify_batch_point_dev.  Expected results: the AND of the per-element ZIP-215 verdicts (the model
 of tests/zip215_cases.py for the special rows, the reference's for honest and corrupted ones, as in tests/test_gpu_verify_zip215.py);
-expected points: tests/batch_eq_model.py.  Every case is a well-formed call."""
+expected points: tests/batch_eq_model.py -- the slow model up to 64 elements, and at every size its closed form for rows whose S is
+moved by a known delta (the host *_batch forms draw their seeds inside the library and cannot be steered: the closed form stays with
+the *_dev forms and the hook).  Every case is a well-formed call."""
 import contextlib
 import ctypes as C
 import threading
@@ -17,6 +19,8 @@ pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 1024, 1025, 4096, 32769, 65537)
 WIDTHS = (8, 10, 13)
+ALL_WIDTHS = tuple(range(7, 14)) + (None,)                  # every width BATCH_EQ_WINDOW takes, and the default one
+FIXED_SPECIAL = (1, 17, 62, 1023, 1024, 4095, 32768, 65536)  # where the valid fixture puts its first special rows
 SEEDS = [bytes([29 * j + 3]) * 32 for j in range(3)]
 
 
@@ -65,7 +69,7 @@ def point_dev(api, sig, pk, msg, seed):
 
 
 @pytest.fixture(scope="module")
-def valid(api, oracle):
+def valid_rows(api, oracle):
     """65537 valid elements: honest signatures with every fourth (key, R) pair of the conformance grid (under 32-byte messages) and the
     24 torsion cases shuffled in; row 0 honest, row 1 and the rows around the sizes' edges special.  The special rows have the model's
     verdict 1, the honest ones the reference's."""
@@ -78,10 +82,17 @@ def valid(api, oracle):
     special = np.concatenate([gsig, tsig]), np.concatenate([gpk, tpk]), np.concatenate([gmsg, tmsg])
     assert zc.zip215_rule(*special).all()
     pos = np.random.default_rng(0xBA7C3).permutation(np.arange(1, n))[:len(special[0])]
-    pos[:8] = [1, 17, 62, 1023, 1024, 4095, 32768, 65536]
+    pos[:8] = FIXED_SPECIAL
     assert len(np.unique(pos)) == len(pos)
     sig[pos], pk[pos], msg[pos] = special
-    return sig, pk, msg
+    return sig, pk, msg, pos
+
+
+@pytest.fixture(scope="module")
+def valid(valid_rows):
+    """(sig, pk, msg) of valid_rows; its fourth entry: the special rows (every other row is honest and exactly valid under the
+    reference's cofactorless equation)"""
+    return valid_rows[:3]
 
 
 @pytest.fixture(scope="module")
@@ -145,12 +156,236 @@ def test_cancelling_pair_inside_a_valid_batch_is_rejected(api, oracle, valid, c)
             assert result_dev(api, *dev(sig, pk, msg), seed) == 0
 
 
-def test_a_million_honest_elements_at_default_tunables(api):
-    n = (1 << 20) + 77
-    sig, pk, msg = dev(*honest(api, n, 0xBA7C6))
+@pytest.fixture(scope="module")
+def million(api):
+    """2^20 + 77 honest elements, signed on the device"""
+    return honest(api, (1 << 20) + 77, 0xBA7C6)
+
+
+def test_a_million_honest_elements_at_default_tunables(api, million):
+    n = len(million[0])
+    sig, pk, msg = dev(*million)
     assert result_dev(api, sig, pk, msg, SEEDS[2]) == 1
     sig[n // 3, 5] ^= 0x20
     assert result_dev(api, sig, pk, msg, SEEDS[2]) == 0
+
+
+# ---- the closed form: exact points and steered accepts at every size ------------------------------------------------------
+
+CLOSED_SIZES = tuple(n for n in SIZES if n >= 63)
+
+
+def s_bytes(sig_row):
+    """S of one signature as a device tensor of 32 bytes"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(sig_row[32:])).cuda()
+
+
+@pytest.fixture(scope="module")
+def shifted(valid_rows):
+    """the valid fixture with S of every honest row moved by an odd 62-bit delta: (sig, rows, deltas, special rows ascending)"""
+    sig, _, _, pos = valid_rows
+    special = np.sort(pos)
+    rows = np.setdiff1d(np.arange(len(sig)), special).tolist()
+    deltas = bm.odd_deltas(len(rows), 0xBA7C9)
+    return bm.shift_s(sig, rows, deltas), rows, deltas, special
+
+
+@pytest.fixture(scope="module")
+def shifted_dev(shifted, valid_dev):
+    return dev(shifted[0])[0], valid_dev[1], valid_dev[2]
+
+
+@pytest.fixture(scope="module")
+def special_share(valid_rows):
+    """seed -> {n: what the special rows below n add to the point of the first n elements}: the slow model, once per seed"""
+    sig, pk, msg, pos = valid_rows
+    special = np.sort(pos)
+    return {seed: bm.subset_points(sig[special], pk[special], msg[special], seed, special, SIZES) for seed in SEEDS}
+
+
+@pytest.fixture(scope="module")
+def shift_sums(shifted):
+    """seed -> the running sums of z_i d_i over the shifted rows: one pass over the challenges per seed, shared by every size"""
+    _, rows, deltas, _ = shifted
+    return {seed: bm.shift_sums(seed, rows, deltas) for seed in SEEDS}
+
+
+@pytest.fixture(scope="module")
+def rejected(valid_rows, shifted):
+    """the shifted batch with three rejected honest rows (S = L, a key and an R that do not decode) inside every size's own stretch,
+    away from its ends: (sig, pk, the shifted rows that stay, their deltas)"""
+    _, pk, _, _ = valid_rows
+    sig, rows, deltas, special = shifted
+    sig, pk = sig.copy(), pk.copy()
+    out, below = [], 0
+    for n in CLOSED_SIZES:
+        if n - below >= 8:
+            for k in (1, 2, 3):
+                row = below + (n - below) * k // 4
+                while row in special or row in out:
+                    row += 1
+                out.append(row)
+        below = n
+    for j, row in enumerate(out):
+        assert 0 < row < SIZES[-1] - 1 and row not in special
+        if j % 3 == 0:
+            sig[row, 32:] = np.frombuffer(bm.L.to_bytes(32, "little"), np.uint8)
+        elif j % 3 == 1:
+            pk[row] = bm.undecodable()
+        else:
+            sig[row, :32] = bm.undecodable()
+    gone = set(out)
+    kept = [(r, d) for r, d in zip(rows, deltas) if r not in gone]
+    return sig, pk, [r for r, _ in kept], [d for _, d in kept]
+
+
+def want_points(sums, share):
+    return {(seed, n): bm.encode(bm.shifted_point(sums[seed], n, share[seed][n])) for seed in SEEDS for n in CLOSED_SIZES}
+
+
+@pytest.fixture(scope="module")
+def want_shifted(shift_sums, special_share):
+    return want_points(shift_sums, special_share)
+
+
+@pytest.fixture(scope="module")
+def rejected_case(rejected, special_share, valid_dev):
+    sig, pk, rows, deltas = rejected
+    return dev(sig, pk) + (valid_dev[2],), want_points({seed: bm.shift_sums(seed, rows, deltas) for seed in SEEDS}, special_share)
+
+
+@pytest.mark.parametrize("c", ALL_WIDTHS)
+def test_shifted_rows_give_the_closed_form_point(api, shifted_dev, want_shifted, c):
+    """every honest row's S moved by a known delta: T = [sum z_i d_i mod L]B plus the special rows' share, byte for byte, at every size
+    from 63, for three seeds.  It holds only if element i gets z_i = SHA-512(seed || le64(i))[:16] and its own k_i, and every element
+    is counted once."""
+    sig, pk, msg = shifted_dev
+    with tunables(**({} if c is None else {"BATCH_EQ_WINDOW": c})):
+        for n in CLOSED_SIZES:
+            for seed in SEEDS:
+                got = point_dev(api, sig[:n], pk[:n], msg[:n], seed)
+                assert np.array_equal(got, want_shifted[seed, n]), (c, n, seed[0])
+
+
+@pytest.mark.parametrize("c", ALL_WIDTHS)
+def test_shifted_rows_without_the_rejected_ones_give_the_closed_form_point(api, rejected_case, c):
+    (sig, pk, msg), want = rejected_case
+    with tunables(**({} if c is None else {"BATCH_EQ_WINDOW": c})):
+        for n in CLOSED_SIZES:
+            for seed in SEEDS:
+                got = point_dev(api, sig[:n], pk[:n], msg[:n], seed)
+                assert np.array_equal(got, want[seed, n]), (c, n, seed[0])
+    with tunables(BATCH_EQ_MIN=1, **({} if c is None else {"BATCH_EQ_WINDOW": c})):
+        assert result_dev(api, sig, pk, msg, SEEDS[0]) == 0
+
+
+def steered_s(valid_rows, shift_sums, seed, n):
+    """(row, S bytes on the device): the last row of the first n elements with the delta that makes sum z_i d_i = 0 mod L over them.
+    The row may be a special one: moving its S adds [z d]B like any other row's."""
+    row = n - 1
+    delta = bm.steering_delta(seed, shift_sums[seed], n, row)
+    return row, s_bytes(bm.shift_s(valid_rows[0][row:row + 1], [0], [delta])[0])
+
+
+@pytest.mark.parametrize("c", WIDTHS)
+def test_a_steered_batch_is_accepted_and_then_every_row_counts(api, valid_rows, shifted, shifted_dev, shift_sums, c):
+    """Who knows the seed can choose one delta so that sum z_i d_i = 0 mod L: the equation then holds (T is an 8-torsion point: the
+    special rows' share) although no honest row is valid, and the result is 1.  This is the defined behaviour of a batch rule under a
+    KNOWN seed -- callers pass secret seeds -- and nothing to be fixed.  It holds only if every z_i and k_i is the right one; and from
+    there, one more step in the S of any single row gives 0: every probed row is in the sums exactly once."""
+    import torch
+    host = shifted[0]
+    sig, pk, msg = shifted_dev
+    work = sig.clone()
+    near_special = [r + d for r in FIXED_SPECIAL for d in (-1, 1)]
+    with tunables(BATCH_EQ_MIN=1, BATCH_EQ_WINDOW=c):
+        for k, n in enumerate(SIZES[1:]):
+            seed = SEEDS[k % 3]
+            last, steered = steered_s(valid_rows, shift_sums, seed, n)
+            work[last, 32:] = steered
+            assert result_dev(api, work[:n], pk[:n], msg[:n], seed) == 1, (c, n)
+            assert api.verify_batch_last_equation() == 1
+            runs = [r for _, r in bm.run_boundary_rows(n, 2 * n, max(256, 1 << c))]      # pts of batcheq_equation
+            rows = bm.probe_rows(n, runs + near_special, seed=0xBA7CA + n + c)
+            assert len(rows) >= min(n, 64)
+            now = host[rows].copy()
+            if last in rows:
+                now[rows.index(last), 32:] = steered.cpu().numpy()
+            bumped = dev(bm.shift_s(now, range(len(rows)), [1] * len(rows))[:, 32:])[0]
+            res = torch.full((4 * len(rows), 1), -7, dtype=torch.int32, device="cuda")     # a result word is 16-byte aligned
+            for j, row in enumerate(rows):
+                keep = work[row, 32:].clone()
+                work[row, 32:] = bumped[j]
+                api.ed25519_VerifyBatch_zip215_dev(res[4 * j:4 * j + 1], work[:n], pk[:n], msg[:n], seed)
+                work[row, 32:] = keep
+            wrong = [rows[j] for j in np.flatnonzero(res.cpu().numpy()[::4, 0] != 0)]
+            assert not wrong, (c, n, wrong)
+            work[last, 32:] = sig[last, 32:]
+    assert torch.equal(work, sig)
+
+
+def test_the_per_element_path_rejects_the_steered_batch(api, valid_rows, shifted_dev, shift_sums):
+    """the default BATCH_EQ_MIN: these sizes take the per-element path, which no steering passes"""
+    sig, pk, msg = shifted_dev
+    work = sig.clone()
+    for k, n in enumerate(SIZES[1:]):
+        seed = SEEDS[k % 3]
+        last, steered = steered_s(valid_rows, shift_sums, seed, n)
+        work[last, 32:] = steered
+        assert result_dev(api, work[:n], pk[:n], msg[:n], seed) == 0, n
+        assert api.verify_batch_last_equation() == 0
+        work[last, 32:] = sig[last, 32:]
+
+
+def test_a_steered_ragged_batch_is_accepted(api, oracle):
+    """4096 messages of 0 .. 300 bytes (0, and the lengths at which the padding of SHA-512(R || A || M) takes one more block, among
+    them) through ed25519_VerifyBatch_zip215_ragged_dev: every S moved, the last one steered -> 1; one more step in one row -> 0.  A k_i
+    hashed over the wrong bytes leaves [z_i (k_i' - k_i)]A_i in T and cannot hide."""
+    import torch
+    n = 4096
+    rng = np.random.default_rng(0xBA7CB)
+    lens = rng.integers(0, 301, n)
+    lens[:12] = [0, 47, 48, 175, 176, 300, 0, 1, 111, 112, 239, 240]
+    lens[n - 3:] = [176, 0, 47]
+    body = rng.integers(0, 256, (n, 300), dtype=np.uint8)
+    messages = [body[i, :lens[i]].tobytes() for i in range(n)]
+    pub, priv = api.ed25519_CreateKeyPair(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+    sig = api.ed25519_SignMessage_ragged(priv, messages)
+    for length in np.unique(lens):                                               # exactly valid, each under its own length
+        at = np.flatnonzero(lens == length)
+        assert oracle.ed25519_verify(sig[at], pub[at], body[at, :length], threads=16).all(), length
+    rows, deltas = list(range(n)), bm.odd_deltas(n, 0xBA7CC)
+    deltas[n - 1] = bm.steering_delta(SEEDS[1], bm.shift_sums(SEEDS[1], rows, deltas), n, n - 1)
+    steered = bm.shift_s(sig, rows, deltas)
+    flat, offsets = api._ragged(messages)
+    d_flat = torch.from_numpy(flat.reshape(-1, 1).copy()).cuda()
+    d_off = torch.from_numpy(offsets.astype(np.int64).reshape(-1, 1)).cuda()
+    d_pk, = dev(pub)
+    res = torch.full((12, 1), -7, dtype=torch.int32, device="cuda")                # (a result word is 16-byte aligned)
+    with tunables(BATCH_EQ_MIN=1):
+        api.ed25519_VerifyBatch_zip215_ragged_dev(res[0:1], dev(steered)[0], d_pk, d_flat, d_off, SEEDS[1])
+        assert api.verify_batch_last_equation() == 1
+        api.ed25519_VerifyBatch_zip215_ragged_dev(res[4:5], dev(bm.shift_s(steered, [1234], [1]))[0], d_pk, d_flat, d_off, SEEDS[1])
+    api.ed25519_VerifyBatch_zip215_ragged_dev(res[8:9], dev(steered)[0], d_pk, d_flat, d_off, SEEDS[1])      # the per-element path
+    assert res.cpu().numpy()[::4, 0].tolist() == [1, 0, 0]
+
+
+def test_a_million_shifted_elements_at_default_tunables(api, million):
+    """2^20 + 77 elements signed on the device, every S moved: the exact point, then the steered accept, at the default width and
+    threshold.  (The signatures are not checked against the reference first: an inexact one fails this test, it cannot hide a failure.)"""
+    sig, pk, msg = million
+    n = len(sig)
+    rows, deltas = range(n), bm.odd_deltas(n, 0xBA7CD)
+    sums = bm.shift_sums(SEEDS[2], rows, deltas)
+    d_sig, d_pk, d_msg = dev(bm.shift_s(sig, rows, deltas), pk, msg)
+    assert np.array_equal(point_dev(api, d_sig, d_pk, d_msg, SEEDS[2]), bm.encode(bm.shifted_point(sums, n)))
+    row = n // 2 + 1
+    d_sig[row, 32:] = s_bytes(bm.shift_s(sig[row:row + 1], [0], [bm.steering_delta(SEEDS[2], sums, n, row)])[0])
+    assert result_dev(api, d_sig, d_pk, d_msg, SEEDS[2]) == 1
+    assert api.verify_batch_last_equation() == 1
+    d_sig[n - 300, 32] ^= 1                                                       # S one step off, far from the steered row
+    assert result_dev(api, d_sig, d_pk, d_msg, SEEDS[2]) == 0
 
 
 # ---- below BATCH_EQ_MIN ---------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """GPU suite (MI355X): ZIP-215 batch verification with coalesced keys -- ed25519_VerifyBatch_zip215_indexed_batch / _dev /
 _ragged_batch / _ragged_dev and the hook c25519_amd_verify_batch_indexed_point_dev.  Expected points: tests/batch_eq_indexed_model.py;
 expected results: the model's for the small shapes, and for every shape what ed25519_VerifyBatch_zip215_dev gives on the gathered keys
-with the same seed.  Every case is a well-formed call."""
+with the same seed.  At scale the point is pinned by the closed form of tests/batch_eq_model.py (rows whose S is moved by a known
+delta), with the rows of the special keys through the coalesced model on that subset.  The host *_batch forms draw their seeds inside
+the library and cannot be steered: the closed form stays with the *_dev form and the hook.  Every case is a well-formed call."""
 import contextlib
 import ctypes as C
 import threading
@@ -20,6 +22,9 @@ pytestmark = pytest.mark.gpu
 HOOK_SHAPES = ((1, 1), (2, 1), (64, 1), (65, 2), (257, 3), (600, 1), (600, 7), (600, 600))
 EQUAL_SHAPES = ((4099, 5), (4099, 300), (32769, 1), (65537, 4096))
 PATTERNS = ("mod", "runs", "random")
+# the closed form: a hot key that sums 65537 terms per 32-bit word, all-distinct keys, and 1024 terms per key under every pattern
+CLOSED_SHAPES = tuple((n, K, "random") for n, K in EQUAL_SHAPES) + ((65537, 1, "mod"), (65537, 65537, "random")) \
+    + tuple(((1 << 18) + 5, 256, pattern) for pattern in PATTERNS)
 WIDTHS = (8, 10, 13, None)
 SEEDS = [bytes([31 * j + 7]) * 32 for j in range(3)]
 MIN_DEFAULT = 1 << 18                   # the default BATCH_EQ_INDEXED_MIN (test_default_tunables pins it)
@@ -198,6 +203,64 @@ def test_result_equals_the_plain_call_on_the_gathered_keys(api, special, n, K):
         d2 = dev(keys, idx2, sig2, msg2)
         for seed in SEEDS:
             assert result_dev(api, *d2, seed) == 0 == plain_result_dev(api, *d2, seed), (n, K)
+
+
+# ---- the closed form: exact points and steered accepts at scale -------------------------------------------------------------
+
+def s_bytes(sig_row):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(sig_row[32:])).cuda()
+
+
+@pytest.mark.parametrize("n,K,pattern", CLOSED_SHAPES)
+def test_shifted_rows_give_the_closed_form_point_and_a_steered_batch_is_accepted(api, oracle, special, n, K, pattern):
+    """Honest keys have prime order, so with every honest row's S moved by a known delta the coalesced point is the un-indexed one,
+    [sum z_i d_i mod L]B, plus the share of the rows under the special keys (no other row names those): the hook's bytes equal it at
+    every width.  Then the last row's delta is chosen so that the sum is 0 mod L: the result is 1 although no honest row is valid --
+    the defined behaviour of a batch rule under a KNOWN seed (callers pass secret ones), nothing to be fixed -- and from there one more
+    step in the S of any single probed row gives 0.  All of it holds only if every z_i, every k_i and every key's merged sum is exact."""
+    import torch
+    seed = SEEDS[(n + K) % 3]
+    keys, idx, sig, msg, _ = make(api, special, n, K, pattern, 0x1DEC + n + K)
+    is_special = np.isin(idx, list(key_plan(n, K)))
+    sp, rows = np.flatnonzero(is_special), np.flatnonzero(~is_special).tolist()
+    assert oracle.ed25519_verify(sig[rows], keys[idx[rows]], msg[rows], threads=16).all()      # exactly valid, cofactorless
+    share = bm._ext(im.batch_point(keys, idx[sp], sig[sp], msg[sp], seed, index=sp)[0]) if len(sp) else bm.NEUTRAL
+    assert bm._affine(bm._mul(8, share)) == (0, 1)
+    deltas = bm.odd_deltas(len(rows), 0x1DED + n + K)
+    host = bm.shift_s(sig, rows, deltas)
+    sums = bm.shift_sums(seed, rows, deltas)
+    want = bm.encode(bm.shifted_point(sums, n, share))
+    dk, di, ds, dm = dev(keys, idx, host, msg)
+    for c in WIDTHS:
+        with tunables(**({} if c is None else {"BATCH_EQ_WINDOW": c})):
+            assert np.array_equal(point_dev(api, dk, di, ds, dm, seed), want), (n, K, pattern, c)
+    last = n - 1
+    steered = s_bytes(bm.shift_s(sig[last:], [0], [bm.steering_delta(seed, sums, n, last)])[0])
+    ds[last, 32:] = steered
+    for c in WIDTHS:
+        with tunables(BATCH_EQ_INDEXED_MIN=1, **({} if c is None else {"BATCH_EQ_WINDOW": c})):
+            assert result_dev(api, dk, di, ds, dm, seed) == 1, (n, K, pattern, c)
+            assert api.verify_batch_last_equation() == 1
+    assert np.array_equal(point_dev(api, dk, di, ds, dm, seed), bm.encode(bm._affine(share)))
+    # every probed row counts: the default width's runs of the digit passes (pts of keyeq_equation) over K keys, then n R's
+    more = [int(r) + d for r in sp[:8] for d in (-1, 1)]
+    for is_r, q in bm.run_boundary_rows(K, K + n, max(256, 1 << (10 if n < 1 << 16 else 13))):
+        more += [q] if is_r else np.flatnonzero(idx == q)[:1].tolist()
+    probe = bm.probe_rows(n, more, seed=0x1DEE + n + K)
+    assert len(probe) >= 64
+    now = host[probe].copy()
+    now[probe.index(last), 32:] = steered.cpu().numpy()
+    bumped = dev(bm.shift_s(now, range(len(probe)), [1] * len(probe))[:, 32:])[0]
+    res = torch.full((4 * len(probe), 1), -7, dtype=torch.int32, device="cuda")    # a result word is 16-byte aligned
+    with tunables(BATCH_EQ_INDEXED_MIN=1):
+        for j, row in enumerate(probe):
+            keep = ds[row, 32:].clone()
+            ds[row, 32:] = bumped[j]
+            api.ed25519_VerifyBatch_zip215_indexed_dev(res[4 * j:4 * j + 1], dk, di, ds, dm, seed)
+            ds[row, 32:] = keep
+    wrong = [probe[j] for j in np.flatnonzero(res.cpu().numpy()[::4, 0] != 0)]
+    assert not wrong, (n, K, pattern, wrong)
 
 
 # ---- rejections -----------------------------------------------------------------------------------------------------------

@@ -151,3 +151,62 @@ def test_rejected_elements_give_zero_and_are_left_out_of_the_point(lib, oracle, 
         assert res == 0 and np.array_equal(got, bm.encode(want)), (what, c)
     # ... and what is left satisfies the equation: the point is in the 8-torsion
     assert bm._affine(bm._mul(8, bm._ext(want))) == (0, 1)
+
+
+# ---- the closed form (tests/batch_eq_model.py): exact points where the buckets fill ----------------------------------------
+# The host *_batch forms draw their seeds inside the library and cannot be steered: they are out of scope here.
+
+CLOSED_FORM = ((1000, 7), (1000, 8), (3000, 10), (3000, 13))               # (n, c): chains in the buckets, the p mod G split, dense chunks
+
+
+@pytest.fixture(scope="module")
+def exact(oracle):
+    """3000 honest signatures, each exactly valid under the reference's cofactorless equation"""
+    sig, pk, msg = honest(oracle, max(n for n, _ in CLOSED_FORM), 0xBA7C4020)
+    assert oracle.ed25519_verify(sig, pk, msg, threads=4).all()
+    return sig, pk, msg
+
+
+@pytest.mark.parametrize("n,c", CLOSED_FORM)
+def test_shifted_rows_give_the_closed_form_point(lib, exact, n, c):
+    """every S moved by an odd 62-bit delta, three rows rejected away from the ends: T = [sum z_i d_i]B over the rows that stay"""
+    sig, pk, msg = (a[:n].copy() for a in exact)
+    out = {n // 3: "S = L", n // 2: "key", 2 * n // 3 + 1: "R"}
+    rows = [i for i in range(n) if i not in out]
+    deltas = bm.odd_deltas(len(rows), 0xBA7C4021 + n + c)
+    sig = bm.shift_s(sig, rows, deltas)
+    for row, what in out.items():
+        if what == "S = L":
+            sig[row, 32:] = np.frombuffer(L.to_bytes(32, "little"), np.uint8)
+        elif what == "key":
+            pk[row] = bm.undecodable()
+        else:
+            sig[row, :32] = bm.undecodable()
+    want = bm.shifted_point(bm.shift_sums(SEEDS[4], rows, deltas), n)
+    got, res = run(lib, sig, pk, msg, SEEDS[4], c)
+    assert res == 0 and np.array_equal(got, bm.encode(want)), (n, c)
+
+
+def any_sampled_row_valid(sig, pk, msg):
+    """the ZIP-215 rule accepts one of five rows on its own (the ends and the middle)"""
+    pick = [0, 1, len(sig) // 2, len(sig) - 2, len(sig) - 1]
+    return zc.zip215_rule(sig[pick], pk[pick], msg[pick]).any()
+
+
+@pytest.mark.parametrize("n,c", CLOSED_FORM)
+def test_a_steered_batch_is_accepted_and_one_more_step_is_not(lib, exact, n, c):
+    """every S moved, the last row's by the delta that makes sum z_i d_i = 0 mod L: no element is valid, T is the neutral element and
+    the result 1 -- the defined behaviour of a batch rule under a KNOWN seed (callers pass secret ones); it holds only if every z_i
+    and every k_i is the right one.  With a middle row's S one further, the result is 0."""
+    sig, pk, msg = (a[:n] for a in exact)
+    rows = list(range(n))
+    deltas = bm.odd_deltas(n, 0xBA7C4022 + n + c)
+    deltas[n - 1] = bm.steering_delta(SEEDS[5], bm.shift_sums(SEEDS[5], rows, deltas), n, n - 1)
+    steered = bm.shift_s(sig, rows, deltas)
+    assert bm.shifted_point(bm.shift_sums(SEEDS[5], rows, deltas), n) == (0, 1)
+    assert not any_sampled_row_valid(steered, pk, msg)
+    got, res = run(lib, steered, pk, msg, SEEDS[5], c)
+    assert res == 1 and np.array_equal(got, bm.encode((0, 1))), (n, c)
+    if (n, c) == CLOSED_FORM[-1]:                                                 # (one such run is enough on the CPU)
+        bumped = bm.shift_s(steered, [n // 2 + 7], [1])
+        assert run(lib, bumped, pk, msg, SEEDS[5], c)[1] == 0, (n, c)

@@ -213,3 +213,64 @@ def test_the_same_bytes_at_two_indices_are_two_points(lib, oracle):
     want, ok = im.batch_point(keys2, idx2, sig, msg, SEEDS[7])
     got, res = run(lib, keys2, idx2, sig, msg, SEEDS[7], 8)
     assert ok and res == 1 and np.array_equal(got, bm.encode(want))
+
+
+# ---- the closed form (tests/batch_eq_model.py): exact points where the buckets fill ----------------------------------------
+# Honest keys have prime order, so the coalesced point of shifted honest rows is the un-indexed one: [sum z_i d_i mod L]B.
+# The host *_batch forms draw their seeds inside the library and cannot be steered: they are out of scope here.
+
+CLOSED_FORM = ((1000, 7), (1000, 8), (3000, 10), (3000, 13))               # (n, c), as tests/test_host_emul_verify_batch.py
+KEY_COUNTS = (1, 7, None)                                                   # one hot key (every term merged), seven, one per element
+
+
+@pytest.fixture(scope="module")
+def exact(oracle):
+    """K -> 3000 honest signatures over K keys (None: 3000), each exactly valid under the reference's cofactorless equation; element i
+    names key i mod K, so the first n elements name the first min(n, K) keys"""
+    out = {}
+    for j, K in enumerate(KEY_COUNTS):
+        keys, idx, sig, msg = honest(oracle, 3000, K or 3000, 0xC0A1E5E0 + 2 * j)
+        assert oracle.ed25519_verify(sig, keys[idx], msg, threads=4).all()
+        out[K] = keys, idx, sig, msg
+    return out
+
+
+@pytest.mark.parametrize("K", KEY_COUNTS)
+@pytest.mark.parametrize("n,c", CLOSED_FORM)
+def test_shifted_rows_give_the_closed_form_point(lib, exact, n, c, K):
+    """every S moved by an odd 62-bit delta, three rows rejected away from the ends: T = [sum z_i d_i]B over the rows that stay"""
+    keys, idx, sig, msg = exact[K]
+    keys, idx, sig, msg = keys[:K or n], idx[:n].copy(), sig[:n], msg[:n]
+    out = {n // 3: "S = L", n // 2: "index", 2 * n // 3 + 1: "R"}
+    rows = [i for i in range(n) if i not in out]
+    deltas = bm.odd_deltas(len(rows), 0xC0A1E5E8 + n + c)
+    sig = bm.shift_s(sig, rows, deltas)
+    for row, what in out.items():
+        if what == "S = L":
+            sig[row, 32:] = np.frombuffer(L.to_bytes(32, "little"), np.uint8)
+        elif what == "index":
+            idx[row] = len(keys)
+        else:
+            sig[row, :32] = bm.undecodable()
+    want = bm.shifted_point(bm.shift_sums(SEEDS[4], rows, deltas), n)
+    got, res = run(lib, keys, idx, sig, msg, SEEDS[4], c)
+    assert res == 0 and np.array_equal(got, bm.encode(want)), (n, c, K)
+
+
+@pytest.mark.parametrize("K", KEY_COUNTS)
+@pytest.mark.parametrize("n,c", CLOSED_FORM)
+def test_a_steered_batch_is_accepted(lib, exact, n, c, K):
+    """every S moved, the last row's by the delta that makes sum z_i d_i = 0 mod L: no element is valid, T is the neutral element and
+    the result 1 -- the defined behaviour of a batch rule under a KNOWN seed (callers pass secret ones); it holds only if every z_i,
+    every k_i and every key's merged sum is the right one"""
+    keys, idx, sig, msg = exact[K]
+    keys, idx, sig, msg = keys[:K or n], idx[:n], sig[:n], msg[:n]
+    rows = list(range(n))
+    deltas = bm.odd_deltas(n, 0xC0A1E5E9 + n + c)
+    deltas[n - 1] = bm.steering_delta(SEEDS[5], bm.shift_sums(SEEDS[5], rows, deltas), n, n - 1)
+    steered = bm.shift_s(sig, rows, deltas)
+    assert bm.shifted_point(bm.shift_sums(SEEDS[5], rows, deltas), n) == (0, 1)
+    pick = [0, 1, n // 2, n - 2, n - 1]
+    assert not zc.zip215_rule(steered[pick], keys[idx[pick]], msg[pick]).any()
+    got, res = run(lib, keys, idx, steered, msg, SEEDS[5], c)
+    assert res == 1 and np.array_equal(got, bm.encode((0, 1))), (n, c, K)
