@@ -64,6 +64,7 @@ SIGNATURES = {
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],
+    "c25519_amd_last_shape": [],
     "c25519_amd_host_register": [_vp, _sz],
     "c25519_amd_host_unregister": [_vp],
     "ed25519_Verify_Init_batch": [_vp, _vp, _sz],
@@ -132,6 +133,7 @@ _RESTYPE = {
     "c25519_amd_verify_batch_last_equation": C.c_long,
     "c25519_amd_verify_last_slow_elements": C.c_long,
     "c25519_amd_verify_check_last_wide": C.c_long,
+    "c25519_amd_last_shape": C.c_long,
     "c25519_amd_x25519_one_peer_last_wide": C.c_long,
     "c25519_amd_x25519_indexed_last_ladder_elements": C.c_long,
     "c25519_amd_tunable_get": C.c_long,

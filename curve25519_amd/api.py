@@ -405,6 +405,14 @@ def ed25519_VerifyBatch_zip215_indexed_ragged(keys, idx, sig, messages, seed=Non
     return (ok.value, verdict) if verdicts else ok.value
 
 
+def last_shape():
+    """(form, lanes per workgroup) of the calling thread's last base call -- X25519, public key, key pair, signature, verification --
+    or None when there is none (include/curve25519_amd.h: c25519_amd_last_shape).  form: 1 one element per workgroup, 2 four lanes
+    per element, 3 one lane per element, 4 one lane per element with the shared inversion as its own launch."""
+    v = int(_lib.load().c25519_amd_last_shape())
+    return None if v < 0 else (v & 0xFF, v >> 8)
+
+
 def base_folding8_table():
     """(256, 3, 32) uint8: the device-generated 8-fold base table in the reference's PA_POINT row order."""
     out = np.empty((256, 3, 32), np.uint8)

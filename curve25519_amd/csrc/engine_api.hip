@@ -209,7 +209,11 @@ void c25519_amd_thread_release(void)
     C25519_API_CALL_OR((void)0);
     c25519_host::helper_pool_slot().reset();              // the pipeline's parked helper threads
     tls().release();
+    c25519_host::last_shape() = -1;
 }
+// test / accounting hook: the kernel form the calling thread's last base call took (include/curve25519_amd.h); no synchronisation,
+// the dispatch wrote it on the host
+long c25519_amd_last_shape(void) { return c25519_host::last_shape(); }
 // ---- unit-test hooks (host pointers) ---------------------------------------------------------------
 int c25519_amd_fe_selftest(unsigned char* out, const unsigned char* a, const unsigned char* b, size_t n, int op)
 {

@@ -176,6 +176,11 @@ using c25519_host::run_batch;
 using c25519_host::run_ragged;
 using c25519_host::bad_arg;
 using c25519_host::tls;
+using c25519_host::note_shape;
+using c25519_host::SHAPE_PER_GROUP;
+using c25519_host::SHAPE_QUAD;
+using c25519_host::SHAPE_LANE;
+using c25519_host::SHAPE_LANE_INVERT;
 
 // the constant tables of the current device, generated once per device per process (engine_fixed_base.hip)
 int base_tables(const u32** limbs, const u32** bytes);

@@ -467,11 +467,13 @@ int curve25519_dh_CalculatePublicKey_fast_dev(void* pk, void* sk, size_t n, void
     if (wide_comb && fixed_base_quad_for(n)) {                // four lanes per element
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));
+        note_shape(SHAPE_QUAD, 64);
         k_x25519_public_fast_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(pk, sk, n, wide);
         C25519_TRY(hipGetLastError());
         return 0;
     }
     if (fixed_base_coop_for(n)) {                             // a few elements: one operation per wave
+        note_shape(SHAPE_PER_GROUP, 64);
         if (wide_comb) {
             const u32* wide = nullptr;
             C25519_RC(wide_tables(&wide));
@@ -484,6 +486,7 @@ int curve25519_dh_CalculatePublicKey_fast_dev(void* pk, void* sk, size_t n, void
     c25519_host::WorkLease lease;
     C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
     const ProjScratch scr = carve_proj((u32*)w, n);
+    note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));
@@ -508,11 +511,13 @@ int c25519_engine::keypair_dev(void* pub, void* priv, const void* sk, const void
     if (!blinding && wide_comb && fixed_base_quad_for(n)) {   // four lanes per element
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));
+        note_shape(SHAPE_QUAD, 64);
         k_ed25519_keypair_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(pub, priv, sk, n, wide);
         C25519_TRY(hipGetLastError());
         return 0;
     }
     if ((!blinding || wide_comb) && fixed_base_coop_for(n)) {   // a few elements: one operation per wave
+        note_shape(SHAPE_PER_GROUP, 64);
         if (wide_comb) {
             const u32* wide = nullptr;
             C25519_RC(wide_tables(&wide));
@@ -527,6 +532,7 @@ int c25519_engine::keypair_dev(void* pub, void* priv, const void* sk, const void
     c25519_host::WorkLease lease;
     C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
     const ProjScratch scr = carve_proj((u32*)w, n);
+    note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));
@@ -568,12 +574,14 @@ int c25519_engine::sign_dev(void* sig, const void* priv, const void* blinding, M
     if (!blinding && wide_comb && fixed_base_quad_for(n)) {   // four lanes per element
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));
+        note_shape(SHAPE_QUAD, 64);
         k_ed25519_sign_quad<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(sig, priv, msgs, n, wide);
         C25519_TRY(hipGetLastError());
         return 0;
     }
     if ((!blinding || wide_comb) && fixed_base_coop_for(n)) {   // a few elements: one operation per wave
         const CallWords cw = msgs.offsets ? CallWords{} : call_record_and_message(n, priv, 64, msgs.base, msgs.fixed);
+        note_shape(SHAPE_PER_GROUP, COOP_SHA_BLOCK);
         if (wide_comb) {
             const u32* wide = nullptr;
             C25519_RC(wide_tables(&wide));
@@ -589,6 +597,7 @@ int c25519_engine::sign_dev(void* sig, const void* priv, const void* blinding, M
     const ProjScratch scr = carve_proj((u32*)w, n);
     u32* a_buf = (u32*)w + proj_words(n);
     u32* r_buf = a_buf + sc_words;
+    note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));

@@ -915,11 +915,13 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
         }
         if (!verify_quad_for(n) && verify_coop_for(n)) {   // a few elements: one launch, three waves per element
             C25519_TRY(hipMemsetAsync(fs.slow_count, 0, 3 * sizeof(u32), stream));
+            note_shape(SHAPE_PER_GROUP, 192);
             (zip215 ? k_ed25519_verify_one_per_group_zip215 : strict ? k_ed25519_verify_one_per_group_strict : k_ed25519_verify_one_per_group)<<<(unsigned)n, 192, 0, stream>>>(
                 fs, verdict, sig, pk, msgs, n, tbl);
             C25519_TRY(hipGetLastError());
         } else if (verify_quad_for(n)) {                   // four lanes per element walk; scalars and points side by side in one launch
             const unsigned sb = grid_for(n, FS_BLOCK);
+            note_shape(SHAPE_QUAD, QW_BLOCK);
             (zip215 ? k_ed25519_verify_quad_prep_zip215 : strict ? k_ed25519_verify_quad_prep_strict : k_ed25519_verify_quad_prep)<<<sb + grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
                 fs, sig, pk, msgs, n, sb);
             C25519_TRY(hipGetLastError());
@@ -927,6 +929,7 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
                 fs, verdict, n, tbl);
             C25519_TRY(hipGetLastError());
         } else {
+            note_shape(SHAPE_LANE, WALK_BLOCK);               // (no inversion on the lattice path: the walk decides)
             (zip215 ? k_ed25519_verify_fast_scalars_zip215 : strict ? k_ed25519_verify_fast_scalars_strict : k_ed25519_verify_fast_scalars)<<<grid_for(n, FS_BLOCK), FS_BLOCK, 0, stream>>>(
                 fs, sig, pk, msgs, n);
             C25519_TRY(hipGetLastError());
@@ -950,6 +953,7 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
         return lease.release();
     }
     tl_last_verify = LastVerify();
+    note_shape(SHAPE_LANE_INVERT, ED_BLOCK);
     k_ed25519_verify_init<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(pk, n, tables, VERIFY_TABLE_WORDS);
     C25519_TRY(hipGetLastError());
     k_ed25519_verify_check<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(scr, sig, pk, msgs, n, tbl, tables, VERIFY_TABLE_WORDS);

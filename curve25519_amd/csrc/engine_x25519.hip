@@ -512,6 +512,7 @@ static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t
 {
     if (x25519_quad_for(n)) {                                 // four lanes per element
         const unsigned grid = grid_for(n, quad::ELEMS_PER_WAVE);
+        note_shape(SHAPE_QUAD, 64);
         if (pk) k_x25519_quad<false><<<grid, 64, 0, stream>>>(out, pk, sk, n);
         else    k_x25519_quad<true><<<grid, 64, 0, stream>>>(out, pk, sk, n);
         C25519_TRY(hipGetLastError());
@@ -519,7 +520,9 @@ static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t
     }
     if (x25519_coop_for(n)) {
         const CallWords cw = call_words(n, pk, sk);
-        if (pk && x25519_two_waves_for(n)) k_x25519_coop2<<<(unsigned)n, 128, 0, stream>>>(out, pk, sk, n, take_done_word(n), cw);
+        const bool two_waves = pk && x25519_two_waves_for(n);
+        note_shape(SHAPE_PER_GROUP, two_waves ? 128 : 64);
+        if (two_waves) k_x25519_coop2<<<(unsigned)n, 128, 0, stream>>>(out, pk, sk, n, take_done_word(n), cw);
         else if (pk) k_x25519_coop<false><<<(unsigned)n, 64, 0, stream>>>(out, pk, sk, n, take_done_word(n), cw);
         else    k_x25519_coop<true><<<(unsigned)n, 64, 0, stream>>>(out, pk, sk, n, take_done_word(n), cw);
         C25519_TRY(hipGetLastError());
@@ -530,13 +533,16 @@ static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t
         c25519_host::WorkLease lease;
         if (!work) C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
         const ProjScratch scr = carve_proj((u32*)w, n);
+        note_shape(SHAPE_LANE_INVERT, XL_BLOCK);
         if (pk) k_x25519_ladder<false><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         else    k_x25519_ladder<true><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         C25519_TRY(hipGetLastError());
         C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
         return work ? 0 : lease.release();
     }
-    switch (x25519_block_for(n)) {
+    const int block = x25519_block_for(n);
+    note_shape(SHAPE_LANE, block);
+    switch (block) {
     case 64:  x25519_launch<64>(out, pk, sk, n, stream); break;
     case 128: x25519_launch<128>(out, pk, sk, n, stream); break;
     case 256: x25519_launch<256>(out, pk, sk, n, stream); break;

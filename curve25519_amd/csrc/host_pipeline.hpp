@@ -247,6 +247,12 @@ struct ShapeHint {
     explicit ShapeHint(size_t n) : saved(batch_shape_hint()) { batch_shape_hint() = n; }
     ~ShapeHint() { batch_shape_hint() = saved; }
 };
+// ... and what that choice was, for c25519_amd_last_shape(): the form in the low byte, the lanes per workgroup of the form's main
+// kernel above it.  Written on the host where the dispatch decides (x25519_dev, the fixed-base device paths, verify_run), per
+// calling thread; -1: no such call yet.
+enum ShapeForm { SHAPE_PER_GROUP = 1, SHAPE_QUAD = 2, SHAPE_LANE = 3, SHAPE_LANE_INVERT = 4 };
+inline long& last_shape() { thread_local long shape = -1; return shape; }
+inline void note_shape(ShapeForm form, unsigned lanes) { last_shape() = (long)form | ((long)lanes << 8); }
 
 // the calling thread's parked helpers (created on the first pipelined call, joined when the thread exits or calls
 // c25519_amd_thread_release())

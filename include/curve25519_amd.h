@@ -422,6 +422,18 @@ long c25519_amd_verify_last_slow_elements(void);
 /* did the calling thread's last ed25519_Verify_Check_* call on this device walk the two wide combs (1) or did the reference-order
  * kernel decide it (0)?  -1: no such call.  Synchronises with that call's stream. */
 long c25519_amd_verify_check_last_wide(void);
+/* which kernel form did the calling thread's last base call take?  Written by curve25519_dh_CreateSharedKey_* /
+ * _CalculatePublicKey_* (ladder and _fast), ed25519_CreateKeyPair_*, ed25519_SignMessage_* (blinded or not) and
+ * ed25519_VerifySignature_*, where the dispatch decides from n (and, inside a *_batch call, from the whole call's n); a *_batch call
+ * that was cut into pieces reports its last piece.  The low byte is the form:
+ *   1  one element per workgroup (one, two or three waves);
+ *   2  four lanes per element;
+ *   3  one lane per element with no inversion launch of its own (X25519: ladder and shared inversion in ONE launch; verification:
+ *      the lattice walk, which needs none);
+ *   4  one lane per element, then the shared inversion as a launch of its own;
+ * bits 8 and up are the lanes per workgroup of the form's main kernel (the ladder, the comb walk, the verification walk).
+ * -1: no such call yet, or c25519_amd_thread_release() since.  Does not synchronise: the value is the host's. */
+long c25519_amd_last_shape(void);
 
 /* bytes of device scratch ed25519_VerifySignature_dev needs for n elements (per-lane 4-fold tables);
  * the library allocates and caches it per host thread (about 2.8 KB per element). */
