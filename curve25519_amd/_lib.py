@@ -36,6 +36,12 @@ SIGNATURES = {
     "ed25519_SignMessage_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp],
     "ed25519_SignMessage_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz],
     "ed25519_SignMessage_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_ClassifyKey_batch": [_vp, _vp, _sz],
+    "ed25519_ClassifyKey_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_PublicKey_to_X25519_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_PublicKey_to_X25519_dev": [_vp, _vp, _vp, _sz, _vp],
+    "ed25519_PrivateKey_to_X25519_batch": [_vp, _vp, _sz],
+    "ed25519_PrivateKey_to_X25519_dev": [_vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

@@ -112,6 +112,38 @@ def ed25519_CreateKeyPair(sk):
     return pub, priv
 
 
+KEY_DECODES, KEY_CANONICAL, KEY_SMALL_ORDER, KEY_TORSION_FREE = 1, 2, 4, 8
+
+
+def ed25519_ClassifyKey(pk):
+    """n x ed25519_ClassifyKey: uint32[n] flags, the OR of KEY_DECODES, KEY_CANONICAL, KEY_SMALL_ORDER and KEY_TORSION_FREE
+    (include/curve25519_amd.h states the rule; libsodium's "valid point" is flags == 11)."""
+    pk = _np(pk, 32, "pk")
+    flags = np.empty(pk.shape[0], np.uint32)
+    _lib.check(_lib.load().ed25519_ClassifyKey_batch(_ptr(flags), _ptr(pk), pk.shape[0]), "ed25519_ClassifyKey_batch")
+    return flags
+
+
+def ed25519_PublicKey_to_X25519(pk):
+    """n x ed25519_PublicKey_to_X25519.  Returns (xpk uint8[n, 32], ok int32[n]): ok = 1 and u = (1 + y) / (1 - y) for a key that
+    decodes, is not of small order and is torsion-free; ok = 0 and 32 zero bytes for any other."""
+    pk = _np(pk, 32, "pk")
+    n = pk.shape[0]
+    xpk = np.empty((n, 32), np.uint8)
+    ok = np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_PublicKey_to_X25519_batch(_ptr(xpk), _ptr(ok), _ptr(pk), n), "ed25519_PublicKey_to_X25519_batch")
+    return xpk, ok
+
+
+def ed25519_PrivateKey_to_X25519(priv):
+    """n x ed25519_PrivateKey_to_X25519: priv uint8[n, 64] (seed || pk) -> uint8[n, 32], the clamped first half of SHA-512(seed)."""
+    priv = _np(priv, 64, "priv")
+    xsk = np.empty((priv.shape[0], 32), np.uint8)
+    _lib.check(_lib.load().ed25519_PrivateKey_to_X25519_batch(_ptr(xsk), _ptr(priv), priv.shape[0]),
+               "ed25519_PrivateKey_to_X25519_batch")
+    return xsk
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -511,6 +543,33 @@ def ed25519_CreateKeyPair_dev(pub, priv, sk):
     args = (_check(pub, 32, "pub", n, device=d), _check(priv, 64, "priv", n, device=d), _check(sk, 32, "sk"))
     with _on(sk) as st:
         _lib.check(_lib.load().ed25519_CreateKeyPair_dev(*args, n, st), "ed25519_CreateKeyPair_dev")
+
+
+def ed25519_ClassifyKey_dev(flags, pk):
+    """Device form of ed25519_ClassifyKey: pk uint8[n, 32], flags int32[n, 1] (read as uint32); asynchronous on torch's current stream."""
+    import torch
+    n, d = pk.shape[0], pk.device
+    args = (_check(flags, 1, "flags", n, dtype=torch.int32, device=d), _check(pk, 32, "pk"))
+    with _on(pk) as st:
+        _lib.check(_lib.load().ed25519_ClassifyKey_dev(*args, n, st), "ed25519_ClassifyKey_dev")
+
+
+def ed25519_PublicKey_to_X25519_dev(xpk, ok, pk):
+    """Device form of ed25519_PublicKey_to_X25519: pk uint8[n, 32], xpk uint8[n, 32], ok int32[n, 1]; asynchronous on torch's
+    current stream."""
+    import torch
+    n, d = pk.shape[0], pk.device
+    args = (_check(xpk, 32, "xpk", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(pk, 32, "pk"))
+    with _on(pk) as st:
+        _lib.check(_lib.load().ed25519_PublicKey_to_X25519_dev(*args, n, st), "ed25519_PublicKey_to_X25519_dev")
+
+
+def ed25519_PrivateKey_to_X25519_dev(xsk, priv):
+    """Device form of ed25519_PrivateKey_to_X25519: priv uint8[n, 64], xsk uint8[n, 32]; asynchronous on torch's current stream."""
+    n, d = priv.shape[0], priv.device
+    args = (_check(xsk, 32, "xsk", n, device=d), _check(priv, 64, "priv"))
+    with _on(priv) as st:
+        _lib.check(_lib.load().ed25519_PrivateKey_to_X25519_dev(*args, n, st), "ed25519_PrivateKey_to_X25519_dev")
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

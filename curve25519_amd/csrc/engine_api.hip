@@ -686,6 +686,37 @@ int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)
                      });
 }
 
+// key classification and conversion to X25519 keys (engine_verify.hip; csrc/ed_keys.cuh)
+int ed25519_ClassifyKey_batch(uint32_t* flags, const unsigned char* pk, size_t n)
+{
+    if (!flags || !pk) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, flags, sizeof(uint32_t) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_ClassifyKey_dev(d[1], d[0], c, st);
+                     });
+}
+
+int ed25519_PublicKey_to_X25519_batch(unsigned char* xpk, int* ok, const unsigned char* pk, size_t n)
+{
+    if (!xpk || !ok || !pk) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, xpk, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_PublicKey_to_X25519_dev(d[1], d[2], d[0], c, st);
+                     });
+}
+
+int ed25519_PrivateKey_to_X25519_batch(unsigned char* xsk, const unsigned char* priv, size_t n)
+{
+    if (!xsk || !priv) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ nullptr, xsk, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_PrivateKey_to_X25519_dev(d[1], d[0], c, st);
+                     });
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

@@ -5,7 +5,7 @@
 // The engine is FIVE translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
 //   engine_x25519.hip      the Montgomery-ladder kernels; curve25519_dh_CreateSharedKey / _CalculatePublicKey (*_dev)
 //   engine_fixed_base.hip  the constant tables; key pairs, signatures, CalculatePublicKey_fast, blinding contexts (*_dev)
-//   engine_verify.hip      verification: lattice path, reference order, two-phase / one key (*_dev)
+//   engine_verify.hip      verification: lattice path, reference order, two-phase / one key; key classification and conversion (*_dev)
 //   engine_batch_eq.hip    ZIP-215 batch verification: one equation per call, a bucket-method multi-scalar multiplication (*_dev, *_batch)
 //   engine_api.hip         library state, unit-test hooks, the host-pointer *_batch forms, the reference's single-call prototypes
 // engine.hip includes all five as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh

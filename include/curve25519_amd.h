@@ -218,13 +218,56 @@ int ed25519_SignMessage_indexed_ragged_batch(unsigned char *sig, const void *ctx
 int ed25519_SignMessage_indexed_ragged_dev(void *sig, const void *ctxs, size_t n_ctx, const void *ctx_index,
                                            const void *msgs, const uint64_t *offsets, size_t n, void *stream);
 
+/* Key classification, and conversion of an Ed25519 identity to the X25519 key of the same secret.
+ * ed25519_ClassifyKey_*: flags[i] is the OR of the bits below for the 32 key bytes pk[i].  Read y = the low 255 bits as a
+ * little-endian integer and sign = bit 255; p = 2^255 - 19, L the order of the base point, O the neutral element (0, 1).
+ *   DECODES       the bytes decode as the ZIP-215 calls decode a key: y is taken mod p (all of [p, 2^255) accepted) and
+ *                 (y^2 - 1) / (d y^2 + 1) has a square root x; the root with parity sign is A's x, and x = 0 whatever sign says.
+ *   CANONICAL     y < p, and not (the decoded x is 0 with sign = 1); for bytes that do not decode: y < p.
+ *   SMALL_ORDER   the bytes decode and [8]A = O (y mod p is one of 0, 1, p - 1, y8, p - y8, y8 the y of a point of order 8).
+ *   TORSION_FREE  the bytes decode and [L]A = O: A lies in the subgroup of prime order.  O itself has both order bits.
+ * Bits 2 and 3 are clear where bit 0 is.  dalek's is_torsion_free is bit 3, is_small_order bit 2; a key passes libsodium's
+ * crypto_core_ed25519_is_valid_point exactly when flags == 11 (canonical, on the curve, not of small order, in the prime-order
+ * subgroup).  That is libsodium's rule as stated here: the stated rule is the contract, the library was not compared with a
+ * libsodium build.  A mixed-order key a*B + T (T of order 2, 4 or 8) has flags 3: it decodes, is canonical and is not of small
+ * order, and only the walk [L]A tells it from an honest key -- which is what a caller who must bound verification latency, or who
+ * will not accept such keys, screens with.
+ * ed25519_PublicKey_to_X25519_*: libsodium's crypto_sign_ed25519_pk_to_curve25519.  ok[i] = 1 exactly when the key decodes, is not
+ * of small order and is torsion-free, (flags & 13) == 9; a canonical encoding is not required.  xpk[i] is then the canonical 32
+ * bytes of u = (1 + y) / (1 - y) mod p, bit 255 clear; otherwise ok[i] = 0 and xpk[i] is 32 zero bytes.  Every row of xpk and ok is
+ * written.  The result is curve25519_dh_CalculatePublicKey of ed25519_PrivateKey_to_X25519's output for the same key pair, so it
+ * can go through curve25519_dh_Peer_Init_* into curve25519_dh_CreateSharedKey_indexed_* (INTEGRATION.md).
+ * ed25519_PrivateKey_to_X25519_*: libsodium's crypto_sign_ed25519_sk_to_curve25519.  priv is n x 64 bytes, the reference's
+ * privKey (seed || public key): xsk[i] = SHA-512(priv[i][0..31])[0..31] with xsk[i][0] &= 248, xsk[i][31] &= 127, xsk[i][31] |= 64;
+ * bytes 32..63 of priv are ignored.  xsk is as secret as the seed: one SHA-512 compression per element, no branch and no address
+ * that depends on the data (what ed25519_Sign_Init_* puts in bytes 0..31 of a signer context).
+ *   n == 0 returns 0; a null pointer is an argument error.  *_dev forms never synchronise and take 16-byte aligned device
+ *   pointers (flags and ok: n x 4 bytes); *_batch forms stage through the calling thread's pipeline like their neighbours.
+ * One lane per key at every n (no per-wave or four-lane form; c25519_amd_last_shape is not written).  The lane's work is the walk
+ * [L]A by the signed non-adjacent form of L: 252 doublings and 45 mixed additions, about 2,100 field products per key, and a call
+ * of a few keys costs one lane's latency of that walk.  Measured (profiles/key_convert_rate.txt): up to 2^16 keys a call takes
+ * 0.58-0.64 ms whatever its size, a call of ONE key 0.59-0.68 ms (ClassifyKey_dev) / 0.62-0.73 ms (PublicKey_to_X25519_dev), where
+ * ed25519_VerifySignature_dev takes 0.13 ms; at 2^20 ClassifyKey_dev runs 125 M keys/s and PublicKey_to_X25519_dev 129 M/s, 1.11 x and
+ * 1.14 x ed25519_VerifySignature_dev of the same build (2^16: 1.18 x / 1.14 x; 2^14: 0.57 x / 0.55 x; 2^10: 0.50 x / 0.48 x);
+ * PrivateKey_to_X25519_dev 10.6 G keys/s at 2^20, 23 us for one key.  Convert a key set once, like Peer_Init, not per record. */
+#define C25519_AMD_KEY_DECODES      1u
+#define C25519_AMD_KEY_CANONICAL    2u
+#define C25519_AMD_KEY_SMALL_ORDER  4u
+#define C25519_AMD_KEY_TORSION_FREE 8u
+int ed25519_ClassifyKey_batch(uint32_t *flags, const unsigned char *pk, size_t n);
+int ed25519_ClassifyKey_dev(void *flags, const void *pk, size_t n, void *stream);
+int ed25519_PublicKey_to_X25519_batch(unsigned char *xpk, int *ok, const unsigned char *pk, size_t n);
+int ed25519_PublicKey_to_X25519_dev(void *xpk, void *ok, const void *pk, size_t n, void *stream);
+int ed25519_PrivateKey_to_X25519_batch(unsigned char *xsk, const unsigned char *priv /* n x 64 */, size_t n);
+int ed25519_PrivateKey_to_X25519_dev(void *xsk, const void *priv, size_t n, void *stream);
+
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
  * element through the reference's own operation order in a kernel behind the walk.  Measured at n = 2^20
  * (profiles/r06_verify_worst_case.txt): all keys on the curve 1.00 x (9.5 ms), ONE off-curve key in the batch 1.15 x (one
  * lane's latency of the reference-order path, about 1.4 ms), one per 256 elements 1.15 x, every second key 1.53 x (the
- * worst case), every key 1.46 x.  Verdicts are the reference's in every case; a caller that must bound latency can pre-screen keys, or keep
- * batches from different senders apart. */
+ * worst case), every key 1.46 x.  Verdicts are the reference's in every case; a caller that must bound latency can pre-screen keys
+ * (ed25519_ClassifyKey_* above: bit C25519_AMD_KEY_DECODES), or keep batches from different senders apart. */
 int ed25519_VerifySignature_batch(int *verdict, const unsigned char *sig, const unsigned char *pk,
                                   const unsigned char *msg, size_t msg_size, size_t n);
 int ed25519_VerifySignature_dev(void *verdict, const void *sig, const void *pk, const void *msg,

@@ -604,6 +604,23 @@ def main():
     to_words(sub(lhs, rhs, "key_ok lhs-rhs"), "key_ok curve equation to_words")
     to_words(sub(y2, carry32(add(FROM_WORDS, FROM_WORDS), "key_ok 2 y_key"), "key_ok y"), "key_ok y to_words")
     print("ZIP-215 coset comparison against contexts (prep, finish, rule 2 per context): ok")
+    # ---- ed_keys.cuh: the walk [L]A from the decoder's (x, y) -- x a fe_carry32 output, y fresh from words -- and the conversion ----
+    x, y = carry32(select(neg(R, "key x neg"), R)), FROM_WORDS
+    A_ypx, A_ymx = carry32(add(y, x)), carry32(sub(y, x, "key Y-X"))
+    A_t2d = mul(mul(x, y, "key xy"), CANON, "key 2dxy")
+    for v in (A_ypx, A_ymx, A_t2d):
+        need(all(v[i] <= R[i] for i in range(10)), "key walk: A's precomputed form not reduced")
+    S = ge_double(x, y, ONE)                                 # the first doubling starts from (x, y, 1) ...
+    for v in S:
+        need(all(v[i] <= R[i] for i in range(10)), "key walk: first doubling not reduced")
+    for v in ge_add(R, R, R, R, select(A_ypx, A_ymx), select(A_ypx, A_ymx), select(neg(A_t2d, "key -2dxy"), A_t2d), None):
+        need(all(v[i] <= R[i] for i in range(10)), "key walk: addition of +-A not reduced")     # ... every later step from reduced S
+    to_words(sub(R, R, "key neutral Y - Z"), "key neutral test to_words")
+    to_words(x, "key x to_words")
+    num, den = carry32(add(ONE, y)), carry32(sub(ONE, y, "key 1 - y"))
+    need(all(num[i] <= R[i] and den[i] <= R[i] for i in range(10)), "key conversion: 1 + y / 1 - y not reduced")
+    to_words(mul(num, R, "key u"), "key u to_words")
+    print("key classification walk [L]A and conversion to X25519: ok")
     quad_section(R)
     print("quad25519 ladder step, addition, doubling, batch-inversion exchange: ok")
     small = coop_section(R)
