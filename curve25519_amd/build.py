@@ -35,7 +35,8 @@ def is_stale() -> bool:
     return any(os.path.getmtime(s) > t for s in _sources())
 
 
-ENGINE_UNITS = ("engine_x25519", "engine_fixed_base", "engine_verify", "engine_batch_eq", "engine_api")     # csrc/engine_common.cuh says which is which
+ENGINE_UNITS = ("engine_x25519", "engine_fixed_base", "engine_verify", "engine_verify_ctx", "engine_keys", "engine_batch_eq",
+                "engine_api")               # csrc/engine_common.cuh says which is which; csrc/engine.hip includes the same seven
 OBJ = os.path.join(PKG, "_obj")             # git-ignored, does not travel: the GPU box gets the linked libraries
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-pragma-unroll-threshold=131072"]
 # -pragma-unroll-threshold: k_batch_invert keeps 16 elements and their prefix products in registers, which needs its
@@ -50,9 +51,10 @@ def _hipcc() -> str:
 
 
 def _compile(units, force=False, verbose=False):
-    """units: [(source stem, object name, extra flags)]; the stale ones are compiled side by side (the engine's translation
-    units take 9-40 s each: ~40 s for all of them instead of 100 s as one), each into a file of its own that is renamed when
-    complete (several ranks of one node may find the library stale at the same time)."""
+    """units: [(source stem, object name, extra flags)]; the stale ones are compiled side by side (device code of the engine's seven
+    translation units on eight cores: engine_batch_eq, engine_keys, engine_api 10-11 s, engine_x25519 25 s, engine_verify_ctx 51 s,
+    engine_verify 61 s, engine_fixed_base 64 s; a forced build of the whole library 92 s; profiles/split_verify_units.txt), each
+    into a file of its own that is renamed when complete (several ranks of one node may find the library stale at the same time)."""
     os.makedirs(OBJ, exist_ok=True)
     newest = max(os.path.getmtime(s) for s in _sources())
     jobs = []
@@ -98,8 +100,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_probe(force: bool = False, level: int = 1) -> str:
-    """the engine alone with the in-kernel cycle probe compiled in (engine_x25519.hip: C25519_CYCLE_PROBE; the other three
-    translation units are the product's objects)"""
+    """the engine alone with the in-kernel cycle probe compiled in (engine_x25519.hip: C25519_CYCLE_PROBE; the other
+    translation units of ENGINE_UNITS are the product's objects)"""
     if not force and os.path.exists(PROBE_LIB) and all(os.path.getmtime(s) <= os.path.getmtime(PROBE_LIB) for s in _sources()):
         return PROBE_LIB
     objs = _compile([("engine_x25519", f"engine_x25519_probe{level}", [f"-DC25519_CYCLE_PROBE={level}"])]

@@ -2,7 +2,7 @@
 //   ed25519_ClassifyKey_*             the four flag bits of a 32-byte Ed25519 key
 //   ed25519_PublicKey_to_X25519_*     u = (1 + y) / (1 - y) of a key that decodes, is not of small order and is torsion-free
 //   ed25519_PrivateKey_to_X25519_*    the clamped first half of SHA-512(seed)
-// engine_verify.hip wraps these in its key kernels; tests/host_emul/key_convert.cpp drives the same functions on the CPU.
+// engine_keys.hip wraps these in its key kernels; tests/host_emul/key_convert.cpp drives the same functions on the CPU.
 //
 // The new work is the walk [L]A for a variable point A: the library's other walks either run over tables built for a fixed point or
 // carry a secret or per-element scalar.  L is public and the same in every lane, so its digits are compile-time data: L in signed

@@ -1,6 +1,6 @@
 // curve25519_amd/csrc/engine_api.hip -- library state and knobs, the argument checks of the *_dev forms, the unit-test hooks, the host-pointer *_batch
 // forms (host_pipeline.hpp) and the reference's single-call prototypes
-// (one of the engine's four translation units: engine_common.cuh says which is which)
+// (one of the engine's translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 
 // ------------------------------------------------------------------------------------------------
@@ -686,7 +686,7 @@ int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)
                      });
 }
 
-// key classification and conversion to X25519 keys (engine_verify.hip; csrc/ed_keys.cuh)
+// key classification and conversion to X25519 keys (engine_keys.hip; csrc/ed_keys.cuh)
 int ed25519_ClassifyKey_batch(uint32_t* flags, const unsigned char* pk, size_t n)
 {
     if (!flags || !pk) return bad_arg("null pointer");

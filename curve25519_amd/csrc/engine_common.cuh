@@ -2,15 +2,17 @@
 // between the kernels of a pass, the completion word, the shared inversion (k_batch_invert, its output encoders, launch_invert)
 // and the host-side helpers of the *_dev entry points (tables, argument checks, launch policy).
 //
-// The engine is FIVE translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
+// The engine is SEVEN translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
 //   engine_x25519.hip      the Montgomery-ladder kernels; curve25519_dh_CreateSharedKey / _CalculatePublicKey (*_dev)
 //   engine_fixed_base.hip  the constant tables; key pairs, signatures, CalculatePublicKey_fast, blinding contexts (*_dev)
-//   engine_verify.hip      verification: lattice path, reference order, two-phase / one key; key classification and conversion (*_dev)
+//   engine_verify.hip      verification per element: the lattice path with its strict and ZIP-215 twins, the reference order (*_dev)
+//   engine_verify_ctx.hip  verification against Verify_Init contexts: Verify_Init, every Verify_Check form (*_dev)
+//   engine_keys.hip        key classification and conversion to X25519 keys (*_dev)
 //   engine_batch_eq.hip    ZIP-215 batch verification: one equation per call, a bucket-method multi-scalar multiplication (*_dev, *_batch)
 //   engine_api.hip         library state, unit-test hooks, the host-pointer *_batch forms, the reference's single-call prototypes
-// engine.hip includes all five as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
-// compile (the same kernels).  Entry points are declared in include/curve25519_amd.h, include/curve25519_dh.h and
-// include/ed25519_signature.h (each cites the reference prototype it replaces).
+// engine.hip includes all seven as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
+// compile (the same kernels; tests/test_build_units.py keeps the two lists and the directory in step).  Entry points are declared in
+// include/curve25519_amd.h, include/curve25519_dh.h and include/ed25519_signature.h (each cites the reference prototype it replaces).
 //
 // The reference pays one field inversion (ecp_Inverse, 254 S + 11 M) per call (curve25519_dh.c:148,
 // ed25519_sign.c:265); here it is shared between several elements with Montgomery's trick:
@@ -230,21 +232,23 @@ inline int inversion_k(size_t n)
 }
 
 // K elements per lane, rounded down to an instantiated group size (inversion_group): the product path passes inversion_k(n), the
-// self-test hook (c25519_amd_batch_invert_selftest_dev) any size
-template <typename Fin>
-int launch_invert_k(const ProjScratch& scr, size_t n, int k, const Fin& fin, hipStream_t stream)
+// self-test hook (c25519_amd_batch_invert_selftest_dev) any size.  MaxK: the largest group this finish is instantiated for (a
+// compile-time cap: the sizes above it do not exist).  values: what to invert, scr.z unless the caller says otherwise.
+template <typename Fin, int MaxK = INV_MAX_K>
+int launch_invert_k(const ProjScratch& scr, size_t n, int k, const Fin& fin, hipStream_t stream, const u32* values = nullptr)
 {
-    const int K = inversion_group(k);
+    const u32* Z = values ? values : scr.z;
+    const int K = inversion_group(std::min(k, MaxK));
     const size_t m = (n + K - 1) / K;
     const unsigned grid = grid_for(m, INV_BLOCK);
     switch (K) {
-        case 16: k_batch_invert<Fin, 16><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        case 14: k_batch_invert<Fin, 14><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        case 12: k_batch_invert<Fin, 12><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        case 8:  k_batch_invert<Fin, 8><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        case 4:  k_batch_invert<Fin, 4><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        case 2:  k_batch_invert<Fin, 2><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
-        default: k_batch_invert<Fin, 1><<<grid, INV_BLOCK, 0, stream>>>(scr.z, scr.prefix, n, m, fin); break;
+        case 16: if constexpr (MaxK >= 16) k_batch_invert<Fin, 16><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        case 14: if constexpr (MaxK >= 14) k_batch_invert<Fin, 14><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        case 12: if constexpr (MaxK >= 12) k_batch_invert<Fin, 12><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        case 8:  k_batch_invert<Fin, 8><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        case 4:  k_batch_invert<Fin, 4><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        case 2:  k_batch_invert<Fin, 2><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
+        default: k_batch_invert<Fin, 1><<<grid, INV_BLOCK, 0, stream>>>(Z, scr.prefix, n, m, fin); break;
     }
     C25519_TRY(hipGetLastError());
     return 0;

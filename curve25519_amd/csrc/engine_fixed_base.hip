@@ -1,6 +1,6 @@
 // curve25519_amd/csrc/engine_fixed_base.hip -- the constant tables (generated on the device at first use) and the fixed-base operations: key pairs,
 // signatures, curve25519_dh_CalculatePublicKey_fast, blinding contexts -- kernels and *_dev entry points
-// (one of the engine's four translation units: engine_common.cuh says which is which)
+// (one of the engine's translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 #include "sign_ctx.cuh"
 

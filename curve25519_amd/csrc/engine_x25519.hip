@@ -1,7 +1,7 @@
 // curve25519_amd/csrc/engine_x25519.hip -- the X25519 kernels (the Montgomery ladder per lane, fused with the shared inversion, per wave, on two
 // waves, on quads; many secrets against one peer key over that key's wide comb) and curve25519_dh_CreateSharedKey_dev /
 // curve25519_dh_CalculatePublicKey_dev / curve25519_dh_CreateSharedKey_one_peer_dev
-// (one of the engine's four translation units: engine_common.cuh says which is which)
+// (one of the engine's translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 #include "x25519_peer.cuh"
 #include "x25519_peer_ctx.cuh"

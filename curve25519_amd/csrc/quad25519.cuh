@@ -405,7 +405,7 @@ C25519_DEV void base_mult_wide(fe& own, const u32* __restrict__ g_wide, const un
 }
 
 // own <- s * B + h * P over TWO wide combs walked together (ge25519.cuh: ge_double_base_mult_wide; the two-phase verification's
-// key comb, engine_verify.hip): 40 additions from the neutral element and the same 4 doublings, the rows of the base point's and
+// key comb, engine_verify_ctx.hip): 40 additions from the neutral element and the same 4 doublings, the rows of the base point's and
 // of P's tables in turn, the next row fetched under the current addition.  colsB / colsP: this lane's parked columns of s and h.
 C25519_DEV void double_base_mult_wide(fe& own, const u32* __restrict__ wideB, const unsigned short* colsB, const u32* __restrict__ wideP,
                                       const unsigned short* colsP, int stride, const Roles& R)

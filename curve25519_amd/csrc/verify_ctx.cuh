@@ -1,7 +1,7 @@
 // curve25519_amd/csrc/verify_ctx.cuh -- ed25519_Verify_Check against MANY contexts in one call (ed25519_Verify_Check_indexed_*):
 // element i is checked against context ctx_index[i] of the call's n_ctx 2080-byte records (Verify_Init's layout: pk || 16 rows of
 // four canonical field elements, read as they are, like the reference: ed25519_verify.c:287-313).  The lane's work is
-// verify_check_lane's (engine_verify.hip) with the key and the rows taken from the element's own context; the comparison with
+// verify_check_lane's (verify_check.cuh) with the key and the rows taken from the element's own context; the comparison with
 // enc(R) happens in k_batch_invert<FinishVerifyIndexed>.  In a header of its own so that tests/host_emul compiles it too.
 //
 // The index is public data (which key a signature claims), so its gather and bounds check take no constant-time care.  An index

@@ -1,5 +1,5 @@
 // curve25519_amd/csrc/verify_ctx_zip215.cuh -- the ZIP-215 verdict against Verify_Init contexts (ed25519_Verify_Check_zip215_*,
-// ed25519_Verify_Check_zip215_indexed_*) WITHOUT decoding R.  The context kernels (engine_verify.hip: k_ed25519_verify_check_indexed,
+// ed25519_Verify_Check_zip215_indexed_*) WITHOUT decoding R.  The context kernels (engine_verify_ctx.hip: k_ed25519_verify_check_indexed,
 // _shared, _wide -- launched as the plain calls launch them) leave T = [S]B - [k]A projectively in scratch.  ZIP-215's rule 4,
 // [8](T - R) = O, says that R lies in the coset T + E[8], E[8] the eight points of small order.  So with y_R = (the low 255 bits of
 // R's string) mod p and sign = bit 255, rules 3 (R decodes) and 4 hold exactly when one of the eight points C = T + t has

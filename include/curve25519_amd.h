@@ -546,7 +546,7 @@ int ed25519_Verify_Check_indexed_ragged_dev(void *verdict, const void *ctxs, siz
  * ed25519_VerifySignature_zip215_dev's kernels: the same verdict by the contract.
  * Measured on MI355X (tools/verify_check_zip215_rate.py, profiles/verify_check_zip215_rate.txt): NOT MEASURED YET -- no device
  * was reached while these calls were built, so the tool has not produced its table and the default of ZIP215_CHECK_MIN is the plain
- * pair's measured crossover (csrc/engine_verify.hip: ZIP215_CHECK_MIN_DEFAULT), not this call's own.  By operation count (5 + 21
+ * pair's measured crossover (csrc/engine_verify_ctx.hip: ZIP215_CHECK_MIN_DEFAULT), not this call's own.  By operation count (5 + 21
  * products and 9 canonicalisations per pair behind a walk of ~1 200 products) the context path should run within a few percent of the
  * plain context calls -- 204-219 M/s over many contexts, 646-664 M/s over one key at 2^20, about 1.8 x
  * ed25519_VerifySignature_zip215_* over many keys; that is a count, not a result. */

@@ -1,6 +1,6 @@
 // tests/host_emul/indexed_check.cpp -- TEST INFRASTRUCTURE.  ed25519_Verify_Check against many contexts
 // (curve25519_amd/csrc/verify_ctx.cuh: what ed25519_Verify_Check_indexed_* runs on the device) driven on the CPU the way
-// engine_verify.hip drives it: k_ed25519_verify_check_indexed's lane (indexed_ctx, verify_ctx_point over the context's rows in place,
+// engine_verify_ctx.hip drives it: k_ed25519_verify_check_indexed's lane (indexed_ctx, verify_ctx_point over the context's rows in place,
 // or over the 128-byte-aligned copy k_ed25519_verify_ctx_repack makes), the projective results in the scratch's SoA layout, then
 // k_batch_invert<FinishVerifyIndexed, K>'s lanes (csrc/batch_invert_lane.inc) in workgroups of 64 lock-step lanes.  The contexts are
 // copied into a buffer of exactly n_ctx x 2080 bytes first, so that a build with -fsanitize=address sees a read past them.

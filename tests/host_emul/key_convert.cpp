@@ -1,5 +1,5 @@
 // tests/host_emul/key_convert.cpp -- TEST INFRASTRUCTURE.  The key calls' lane functions (curve25519_amd/csrc/ed_keys.cuh) driven on
-// the CPU the way engine_verify.hip drives them per lane: k_ed25519_key_classify's ed_key_classify, k_ed25519_key_to_x25519's
+// the CPU the way engine_keys.hip drives them per lane: k_ed25519_key_classify's ed_key_classify, k_ed25519_key_to_x25519's
 // ed_key_to_x25519_lane with FinishKeyX25519 behind a plain fe_invert (the shared inversion's answer, 0 for a zero denominator),
 // k_ed25519_private_to_x25519's ed_key_private_to_x25519, and the walk's pieces on their own for the property tests.  Built into
 // its own library by tests/test_host_emul_key_convert.py through tests/host_emul/build.py's open_lib.  Not part of the product.

@@ -1,5 +1,5 @@
 // tests/host_emul/verify_check_zip215.cpp -- TEST INFRASTRUCTURE.  The coset comparison of ed25519_Verify_Check_zip215_*
-// (curve25519_amd/csrc/verify_ctx_zip215.cuh) driven on the CPU the way engine_verify.hip drives it behind the walk: the coset prep's
+// (curve25519_amd/csrc/verify_ctx_zip215.cuh) driven on the CPU the way engine_verify_ctx.hip drives it behind the walk: the coset prep's
 // lane (coset_prep_element) over projective points in the scratch's SoA layout, then k_batch_invert<FinishVerifyZip215, K>'s lanes
 // (csrc/batch_invert_lane.inc) over the products it left, in workgroups of 64 lock-step lanes; and the per-context rule 2
 // (zip215_ctx_key_ok).  The points come from the caller (tests/check_zip215_model.py computes T = [S]B - [k]A in big integers and

@@ -5,7 +5,7 @@ import pytest
 from kernel_usage import spill_free, usage  # noqa: F401
 
 PLAIN = ["k_ed25519_verify_coset_prep", "k_ed25519_verify_coset_key_gather", "k_ed25519_verify_coset_index_mask"]
-GROUPS = [12, 8, 4, 2, 1]          # launch_coset_finish (engine_verify.hip): this finish is instantiated up to 12 elements per lane
+GROUPS = [12, 8, 4, 2, 1]          # launch_coset_finish (engine_verify_ctx.hip): this finish is instantiated up to 12 elements per lane
 
 
 @pytest.mark.parametrize("name", PLAIN)
