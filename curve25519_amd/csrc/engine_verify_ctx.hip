@@ -331,7 +331,8 @@ __global__ void __launch_bounds__(ZC_BLOCK) k_ed25519_verify_coset_index_mask(in
 namespace {
 
 // what the calling thread's last ed25519_Verify_Check_* call on this device left behind for c25519_amd_verify_check_last_wide:
-// where its "the two wide combs decide this batch" word lives (null: the call never asked)
+// where its "the two wide combs decide this batch" word lives (null: the call never asked) -- one of the slab's report words, which
+// no call's scratch overlaps: the word is the call's own and still there when later calls of other kinds have reused the slab
 struct LastCheck { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
 thread_local LastCheck tl_last_check;
 
@@ -425,6 +426,7 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
     const bool try_wide = build || reuse;
     tl_last_check = LastCheck();
     tl_last_check.ran = true;
+    tl_last_check.generation = tls().generation;
     if (!zip215 && !try_wide && small) {                    // a few pairs: one per wave, the reference's order
         k_ed25519_verify_check_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctx, msgs, n, tbl, take_done_word(n));
         C25519_TRY(hipGetLastError());
@@ -442,7 +444,8 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
         C25519_RC(wide_tables(&wide_base));
         // the key's comb and the context it was built for live in a buffer of the calling thread that outlives the call
         // (ThreadState::keep): the next call with the same context bytes finds them there.  The verdict on THIS call's context
-        // (wide_ok) is the call's own: a word of its work scratch.
+        // (wide_ok) is the call's own: a report word of its work slab (word 0 is the fast verification's slow-list count, word 1 the
+        // indexed X25519 call's ladder count), ordered between streams like the slab itself.
         void* keep = nullptr;
         bool fresh = false;
         constexpr size_t KEEP_WORDS = WB_TBL_WORDS + 16 * 32 + KEEP_CTX_WORDS + 1 + 3;
@@ -450,7 +453,9 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
         u32* wide_key = (u32*)keep;
         u32* check_rows = wide_key + WB_TBL_WORDS;
         u32* remembered = check_rows + 16 * 32;
-        wide_ok = (u32*)w + proj_words(n);                  // (16-byte aligned: proj_words is a multiple of 4)
+        unsigned* report = nullptr;
+        C25519_RC(tls().report_word_for(&report, stream));
+        wide_ok = report + 2;
         tl_last_check.wide_ok = wide_ok; tl_last_check.stream = stream; tl_last_check.generation = tls().generation;
         (void)hipGetDevice(&tl_last_check.device);
         k_ed25519_verify_ctx_prepare<<<build ? 1 + WB_NT * WB_ROWS / 128 : 1, 128, 0, stream>>>(wide_key, check_rows, wide_ok, (const u32*)ctx, remembered, build ? 1 : 0);
@@ -576,6 +581,7 @@ int ed25519_Verify_Check_zip215_dev(void* verdict, const void* ctx, const void* 
     if (!zip215_check_walks(n)) {
         tl_last_check = LastCheck();
         tl_last_check.ran = true;
+        tl_last_check.generation = tls().generation;
         return zip215_check_gathered((int*)verdict, ctx, 1, nullptr, sig, fixed_msgs(msg, msg_size), n, (hipStream_t)stream_);
     }
     return verify_check_one_dev(verdict, ctx, sig, msg, msg_size, n, (hipStream_t)stream_, true);
@@ -605,10 +611,10 @@ long c25519_amd_verify_check_last_wide(void)
 {
     C25519_API_CALL_OR(-1);
     const LastCheck& lc = tl_last_check;
-    if (!lc.ran) return -1;
+    if (!lc.ran || lc.generation != tls().generation) return -1;    // (c25519_amd_thread_release() / a device switch since)
     if (!lc.wide_ok) return 0;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != lc.device || lc.generation != tls().generation) return -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != lc.device) return -1;
     if (hipStreamSynchronize(lc.stream) != hipSuccess) return -1;
     u32 v = 0;
     if (hipMemcpy(&v, lc.wide_ok, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;

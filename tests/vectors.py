@@ -2,6 +2,8 @@
 results computed by Python big integers.  The cases follow the reference's own unit checks
 (test/curve25519_selftest.c:624-741): field identities mod p, and mod-L reductions around the n*L +- 1 and
 b*R +- 1 boundaries where eco_ReduceHiWord / eco_Mod take their borrow paths."""
+import functools
+
 import numpy as np
 
 from curve25519_amd import synth
@@ -166,6 +168,7 @@ def ed_enc(p):
     return (p[1] | ((p[0] & 1) << 255)).to_bytes(32, "little")
 
 
+@functools.lru_cache(maxsize=1024)       # (a model that decodes one key for every row of a set pays for the square root once)
 def ed_decode(y, sign):
     u, v = (y * y - 1) % P, (D_ED * y * y + 1) % P
     x = pow(u * pow(v, P - 2, P) % P, (P + 3) // 8, P)
