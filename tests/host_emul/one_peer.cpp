@@ -78,6 +78,31 @@ void emul_one_peer_rows(unsigned* out, const unsigned char* q_in, const unsigned
     });
 }
 
+// the peer's comb in the device layout with only the rows that the n clamped secrets k (8 words each) select: the columns of every
+// secret (k >> 3, as x25519_one_peer_lane recodes it), then the rows of those columns by emul_one_peer_rows
+static void one_peer_needed_rows(std::vector<u32>& wide_peer, const u32 (&q)[3][8], const std::vector<u32>& k, size_t n)
+{
+    std::vector<unsigned short> cols(WB_COLS * n);
+    for (size_t i = 0; i < n; i++) {
+        u32 kw[8], k3[8];
+        memcpy(kw, &k[8 * i], 32);
+        for (int j = 0; j < 7; j++) k3[j] = (kw[j] >> 3) | (kw[j + 1] << 29);
+        k3[7] = kw[7] >> 3;
+        wb_columns(&cols[WB_COLS * i], 1, k3);
+    }
+    std::vector<char> need((size_t)WB_NT * WB_ROWS, 0);
+    for (size_t i = 0; i < n; i++)
+        for (int m = 0; m < WB_STEP; m++)
+            for (int t = 0; t < WB_NT; t++) need[row_of(t, cols[WB_COLS * i + m * WB_NT + t])] = 1;
+    std::vector<unsigned> idx;
+    for (size_t g = 0; g < need.size(); g++)
+        if (need[g]) idx.push_back((unsigned)g);
+    std::vector<u32> rows(idx.size() * WB_ROW_WORDS);
+    wide_peer.assign(WB_TBL_WORDS, 0);
+    emul_one_peer_rows(rows.data(), reinterpret_cast<const unsigned char*>(q), idx.data(), idx.size());
+    for (size_t r = 0; r < idx.size(); r++) memcpy(&wide_peer[(size_t)idx[r] * WB_ROW_WORDS], &rows[r * WB_ROW_WORDS], WB_ROW_WORDS * 4);
+}
+
 // curve25519_dh_CreateSharedKey_one_peer for n secrets against the one key pk, sk clamped in place.  Returns 1 if the comb decided
 // (the peer is eligible), 0 if the ladder did (x25519_ladder_xz per secret, as k_x25519_ladder_one_peer).
 int emul_one_peer(unsigned char* out, const unsigned char* pk, unsigned char* sk, size_t n)
@@ -106,25 +131,9 @@ int emul_one_peer(unsigned char* out, const unsigned char* pk, unsigned char* sk
         });
         return 0;
     }
-    // the columns of every secret (k >> 3, as x25519_one_peer_lane recodes it), then the rows they select
+    std::vector<u32> wide_peer;
+    one_peer_needed_rows(wide_peer, q, k, n);
     std::vector<unsigned short> cols(WB_COLS * n);
-    for (size_t i = 0; i < n; i++) {
-        u32 kw[8], k3[8];
-        memcpy(kw, &k[8 * i], 32);
-        for (int j = 0; j < 7; j++) k3[j] = (kw[j] >> 3) | (kw[j + 1] << 29);
-        k3[7] = kw[7] >> 3;
-        wb_columns(&cols[WB_COLS * i], 1, k3);
-    }
-    std::vector<char> need((size_t)WB_NT * WB_ROWS, 0);
-    for (size_t i = 0; i < n; i++)
-        for (int m = 0; m < WB_STEP; m++)
-            for (int t = 0; t < WB_NT; t++) need[row_of(t, cols[WB_COLS * i + m * WB_NT + t])] = 1;
-    std::vector<unsigned> idx;
-    for (size_t g = 0; g < need.size(); g++)
-        if (need[g]) idx.push_back((unsigned)g);
-    std::vector<u32> rows(idx.size() * WB_ROW_WORDS), wide_peer(WB_TBL_WORDS, 0);
-    emul_one_peer_rows(rows.data(), reinterpret_cast<const unsigned char*>(q), idx.data(), idx.size());
-    for (size_t r = 0; r < idx.size(); r++) memcpy(&wide_peer[(size_t)idx[r] * WB_ROW_WORDS], &rows[r * WB_ROW_WORDS], WB_ROW_WORDS * 4);
     parallel_for(n, [&](size_t i) {
         u32 kw[8], w[8];
         memcpy(kw, &k[8 * i], 32);

@@ -117,14 +117,14 @@ inline u64 mad64(u64 acc, u32 x, u32 y)
     __atomic_fetch_add(&emul_mad_count, 1ULL, __ATOMIC_RELAXED);
     const u64 p = (u64)x * y;
     const u64 r = acc + p;
-    if (r < acc) emul_mad_overflows++;
+    __atomic_fetch_add(&emul_mad_overflows, (unsigned long long)(r < acc), __ATOMIC_RELAXED);      // (branch-free: the model never branches on data)
     return r;
 }
 inline int64_t mad_i64_i32(int64_t acc, int32_t x, int32_t y)      // v_mad_i64_i32; a signed wrap would break safegcd25519.cuh's bounds
 {
     __atomic_fetch_add(&emul_mad_count, 1ULL, __ATOMIC_RELAXED);
     int64_t r;
-    if (__builtin_add_overflow(acc, (int64_t)x * y, &r)) emul_mad_overflows++;
+    __atomic_fetch_add(&emul_mad_overflows, (unsigned long long)__builtin_add_overflow(acc, (int64_t)x * y, &r), __ATOMIC_RELAXED);
     return r;
 }
 inline int64_t mad2_i64_i32(int64_t acc, int32_t x0, int32_t y0, int32_t x1, int32_t y1) { return mad_i64_i32(mad_i64_i32(acc, x0, y0), x1, y1); }
