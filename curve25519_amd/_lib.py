@@ -42,6 +42,18 @@ SIGNATURES = {
     "ed25519_PublicKey_to_X25519_dev": [_vp, _vp, _vp, _sz, _vp],
     "ed25519_PrivateKey_to_X25519_batch": [_vp, _vp, _sz],
     "ed25519_PrivateKey_to_X25519_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_ScalarMult_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarMult_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarMult_noclamp_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarMult_noclamp_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarMultBase_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarMultBase_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_ScalarMultBase_noclamp_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarMultBase_noclamp_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_PointAdd_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

@@ -144,6 +144,56 @@ def ed25519_PrivateKey_to_X25519(priv):
     return xsk
 
 
+def _group_pairs(a, b, names):
+    a, b = _np(a, 32, names[0]), _np(b, 32, names[1])
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"{names[0]} and {names[1]} must have the same number of rows")
+    return a, b
+
+
+def ed25519_ScalarMult(scalar, point, clamp=True):
+    """n x ed25519_ScalarMult (clamp=False: ed25519_ScalarMult_noclamp).  Returns (q uint8[n, 32], ok int32[n]): ok = 1 and
+    q = enc([e]P) where the point bytes decode (the ZIP-215 rule), ok = 0 and 32 zero bytes where they do not; e is the scalar
+    clamped on a copy, or its low 255 bits.  The scalar is not modified."""
+    scalar, point = _group_pairs(scalar, point, ("scalar", "point"))
+    n = scalar.shape[0]
+    q, ok = np.empty((n, 32), np.uint8), np.empty(n, np.int32)
+    L = _lib.load()
+    fn = L.ed25519_ScalarMult_batch if clamp else L.ed25519_ScalarMult_noclamp_batch
+    _lib.check(fn(_ptr(q), _ptr(ok), _ptr(scalar), _ptr(point), n), "ed25519_ScalarMult_batch")
+    return q, ok
+
+
+def ed25519_ScalarMultBase(scalar, clamp=True):
+    """n x ed25519_ScalarMultBase (clamp=False: ed25519_ScalarMultBase_noclamp): uint8[n, 32], enc([e]B) for every scalar."""
+    scalar = _np(scalar, 32, "scalar")
+    q = np.empty((scalar.shape[0], 32), np.uint8)
+    L = _lib.load()
+    fn = L.ed25519_ScalarMultBase_batch if clamp else L.ed25519_ScalarMultBase_noclamp_batch
+    _lib.check(fn(_ptr(q), _ptr(scalar), scalar.shape[0]), "ed25519_ScalarMultBase_batch")
+    return q
+
+
+def _point_add(p, q, sub):
+    p, q = _group_pairs(p, q, ("p", "q"))
+    n = p.shape[0]
+    r, ok = np.empty((n, 32), np.uint8), np.empty(n, np.int32)
+    L = _lib.load()
+    fn = L.ed25519_PointSub_batch if sub else L.ed25519_PointAdd_batch
+    _lib.check(fn(_ptr(r), _ptr(ok), _ptr(p), _ptr(q), n), "ed25519_PointSub_batch" if sub else "ed25519_PointAdd_batch")
+    return r, ok
+
+
+def ed25519_PointAdd(p, q):
+    """n x ed25519_PointAdd.  Returns (r uint8[n, 32], ok int32[n]): ok = 1 and r = enc(P + Q) where both decode, else zeros."""
+    return _point_add(p, q, False)
+
+
+def ed25519_PointSub(p, q):
+    """n x ed25519_PointSub.  Returns (r uint8[n, 32], ok int32[n]): ok = 1 and r = enc(P - Q) where both decode, else zeros."""
+    return _point_add(p, q, True)
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -570,6 +620,50 @@ def ed25519_PrivateKey_to_X25519_dev(xsk, priv):
     args = (_check(xsk, 32, "xsk", n, device=d), _check(priv, 64, "priv"))
     with _on(priv) as st:
         _lib.check(_lib.load().ed25519_PrivateKey_to_X25519_dev(*args, n, st), "ed25519_PrivateKey_to_X25519_dev")
+
+
+def ed25519_ScalarMult_dev(q, ok, scalar, point, clamp=True):
+    """Device form of ed25519_ScalarMult (clamp=False: _noclamp): scalar, point, q uint8[n, 32], ok int32[n, 1]; asynchronous on
+    torch's current stream.  The scalar is not written."""
+    import torch
+    L = _lib.load()
+    fn = L.ed25519_ScalarMult_dev if clamp else L.ed25519_ScalarMult_noclamp_dev
+    n, d = scalar.shape[0], scalar.device
+    args = (_check(q, 32, "q", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(scalar, 32, "scalar"),
+            _check(point, 32, "point", n, device=d))
+    with _on(scalar) as st:
+        _lib.check(fn(*args, n, st), "ed25519_ScalarMult_dev")
+
+
+def ed25519_ScalarMultBase_dev(q, scalar, clamp=True):
+    """Device form of ed25519_ScalarMultBase (clamp=False: _noclamp): scalar, q uint8[n, 32]; asynchronous on torch's current stream."""
+    L = _lib.load()
+    fn = L.ed25519_ScalarMultBase_dev if clamp else L.ed25519_ScalarMultBase_noclamp_dev
+    n, d = scalar.shape[0], scalar.device
+    args = (_check(q, 32, "q", n, device=d), _check(scalar, 32, "scalar"))
+    with _on(scalar) as st:
+        _lib.check(fn(*args, n, st), "ed25519_ScalarMultBase_dev")
+
+
+def _point_add_dev(r, ok, p, q, sub):
+    import torch
+    L = _lib.load()
+    fn = L.ed25519_PointSub_dev if sub else L.ed25519_PointAdd_dev
+    n, d = p.shape[0], p.device
+    args = (_check(r, 32, "r", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(p, 32, "p"),
+            _check(q, 32, "q", n, device=d))
+    with _on(p) as st:
+        _lib.check(fn(*args, n, st), "ed25519_PointSub_dev" if sub else "ed25519_PointAdd_dev")
+
+
+def ed25519_PointAdd_dev(r, ok, p, q):
+    """Device form of ed25519_PointAdd: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    _point_add_dev(r, ok, p, q, False)
+
+
+def ed25519_PointSub_dev(r, ok, p, q):
+    """Device form of ed25519_PointSub: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    _point_add_dev(r, ok, p, q, True)
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

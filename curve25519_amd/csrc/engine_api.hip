@@ -717,6 +717,61 @@ int ed25519_PrivateKey_to_X25519_batch(unsigned char* xsk, const unsigned char* 
                      });
 }
 
+// the group operations (engine_group.hip; csrc/ed_group.cuh)
+static int scalarmult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n, bool clamp)
+{
+    if (!q || !ok || !scalar || !point) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    const auto call_dev = clamp ? ed25519_ScalarMult_dev : ed25519_ScalarMult_noclamp_dev;
+    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ point, nullptr, 32 }, Arr{ nullptr, q, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
+}
+
+int ed25519_ScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
+{
+    return scalarmult_batch(q, ok, scalar, point, n, true);
+}
+
+int ed25519_ScalarMult_noclamp_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
+{
+    return scalarmult_batch(q, ok, scalar, point, n, false);
+}
+
+static int scalarmult_base_batch(unsigned char* q, const unsigned char* scalar, size_t n, bool clamp)
+{
+    if (!q || !scalar) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    const auto call_dev = clamp ? ed25519_ScalarMultBase_dev : ed25519_ScalarMultBase_noclamp_dev;
+    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ nullptr, q, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], c, st); });
+}
+
+int ed25519_ScalarMultBase_batch(unsigned char* q, const unsigned char* scalar, size_t n) { return scalarmult_base_batch(q, scalar, n, true); }
+
+int ed25519_ScalarMultBase_noclamp_batch(unsigned char* q, const unsigned char* scalar, size_t n)
+{
+    return scalarmult_base_batch(q, scalar, n, false);
+}
+
+static int point_add_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n, bool sub)
+{
+    if (!r || !ok || !p || !q) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    const auto call_dev = sub ? ed25519_PointSub_dev : ed25519_PointAdd_dev;
+    return run_batch(n, { Arr{ p, nullptr, 32 }, Arr{ q, nullptr, 32 }, Arr{ nullptr, r, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
+}
+
+int ed25519_PointAdd_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
+{
+    return point_add_batch(r, ok, p, q, n, false);
+}
+
+int ed25519_PointSub_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
+{
+    return point_add_batch(r, ok, p, q, n, true);
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

@@ -53,7 +53,8 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * of more than 3584 elements with the peer the calling thread's last comb was built for walks that comb whatever its size;
  * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
- * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there).
+ * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there), SCALARMULT_WINDOW
+ * (ed25519_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -260,6 +261,54 @@ int ed25519_PublicKey_to_X25519_batch(unsigned char *xpk, int *ok, const unsigne
 int ed25519_PublicKey_to_X25519_dev(void *xpk, void *ok, const void *pk, size_t n, void *stream);
 int ed25519_PrivateKey_to_X25519_batch(unsigned char *xsk, const unsigned char *priv /* n x 64 */, size_t n);
 int ed25519_PrivateKey_to_X25519_dev(void *xsk, const void *priv, size_t n, void *stream);
+
+/* Group operations on Ed25519 points: libsodium's crypto_scalarmult_ed25519[_noclamp], crypto_scalarmult_ed25519_base[_noclamp] and
+ * crypto_core_ed25519_add / _sub, dalek's EdwardsPoint * Scalar -- what key blinding, hierarchical child keys (A + [z]B), threshold
+ * and adaptor signatures and Diffie-Hellman on Edwards keys are built from.  Points and scalars are n x 32 bytes, ok is n x int.
+ *   Decoding.  A point decodes exactly as ed25519_ClassifyKey_*'s DECODES bit says: the ZIP-215 rule, y = the low 255 bits taken
+ *     mod p, x the square root of (y^2 - 1) / (d y^2 + 1) with the parity of bit 255, and x = 0 whatever that bit says.
+ *   Scalar.  e is the 32-byte scalar clamped on a COPY (byte 0 &= 248, byte 31 &= 127, byte 31 |= 64); for the _noclamp calls e is the
+ *     low 255 bits: bit 255 is ignored, as libsodium ignores it.  The caller's scalar bytes are never written (the X25519 calls
+ *     clamp theirs in place; these do not).
+ *   ed25519_ScalarMult[_noclamp]_*: ok[i] = 1 exactly when point[i] decodes, and q[i] is then the canonical encoding of [e]P: y < p
+ *     little-endian, bit 255 the parity of x, clear for x = 0; the neutral element is 01 00 .. 00 with ok = 1.  Otherwise ok[i] = 0
+ *     and q[i] is 32 zero bytes.  Every row of q and ok is written.  No rule on the point's order and none on canonical input is
+ *     applied.  libsodium's call returns 0 with the same bytes exactly when ed25519_ClassifyKey_* gives flags == 11 for the point and
+ *     q is not the neutral encoding; that is libsodium's rule as stated here: the stated rule is the contract, the library was not
+ *     compared with a libsodium build.  A _noclamp result on a mixed-order point reveals the scalar mod 8 (the clamped calls multiply
+ *     by a multiple of 8); ed25519_ClassifyKey_* screens for such points.
+ *   ed25519_ScalarMultBase[_noclamp]_*: q[i] = enc([e]B) for every 32-byte scalar (e = 0 gives the neutral encoding).
+ *   ed25519_PointAdd_* / ed25519_PointSub_*: ok[i] = 1 exactly when p[i] and q[i] both decode, and then r[i] = enc(P + Q) / enc(P - Q);
+ *     otherwise r[i] is 32 zero bytes and ok[i] = 0.
+ *   Secrecy.  The scalar is secret, points are public.  In ed25519_ScalarMult* no branch condition and no load or store address
+ *     derives from the scalar, not even a row fetch: the walk keeps its table of multiples of P in registers and selects a row by
+ *     masks over all of them.  ed25519_ScalarMultBase* fetches the base comb's rows by secret index, exactly as key pairs and signing
+ *     do.
+ *   n == 0 returns 0; a null pointer is an argument error.  *_dev forms never synchronise and take 16-byte aligned device
+ *   pointers; *_batch forms stage through the calling thread's pipeline like their neighbours.
+ * One lane per element at every n (no per-wave or four-lane form; c25519_amd_last_shape is not written), so a call of a few
+ * elements costs one lane's latency of the walk.  ed25519_ScalarMult* recodes e into signed W-bit digits and walks 129 / 86 / 65 of
+ * them for W = 2 / 3 / 4 (tunable SCALARMULT_WINDOW), about 2,840 / 2,520 / 2,400 field products per element against the X25519
+ * ladder's 2,550.  Measured (profiles/group_ops_rate.txt, interleaved rounds): at 2^20 ScalarMult_dev runs 90.4 M/s at W = 2 (11.60 ms),
+ * 86.3 at W = 3, 87.5 at W = 4, against 130.8 M/s for curve25519_dh_CreateSharedKey_dev of the same build on the same n: 0.69 x /
+ * 0.66 x / 0.67 x the ladder, not the 0.85-1.15 x the counts had suggested (the walk holds two waves per SIMD at W = 2 and one at
+ * W = 3 and 4, the ladder four).  W = 2 wins by 0.39 ms where the rounds spread over 0.07 ms, so it is the built-in width.  Up to 2^16
+ * elements a call is one lane's latency of the walk, 0.85-0.86 ms at W = 2 (0.78 at W = 3, 0.76-0.78 at W = 4: the wider windows are
+ * the shorter walks where latency counts), a call of ONE element 0.86-1.02 ms; the _noclamp calls cost the same.
+ * ScalarMultBase_dev: 1.29-1.31 G/s at 2^20, 0.08-0.09 ms up to 2^16, one element 86-96 us.  PointAdd_dev / PointSub_dev: 658-667 M/s
+ * at 2^20, 0.15 ms up to 2^16, one element 0.15-0.17 ms. */
+int ed25519_ScalarMult_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t n);
+int ed25519_ScalarMult_dev(void *q, void *ok, const void *scalar, const void *point, size_t n, void *stream);
+int ed25519_ScalarMult_noclamp_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t n);
+int ed25519_ScalarMult_noclamp_dev(void *q, void *ok, const void *scalar, const void *point, size_t n, void *stream);
+int ed25519_ScalarMultBase_batch(unsigned char *q, const unsigned char *scalar, size_t n);
+int ed25519_ScalarMultBase_dev(void *q, const void *scalar, size_t n, void *stream);
+int ed25519_ScalarMultBase_noclamp_batch(unsigned char *q, const unsigned char *scalar, size_t n);
+int ed25519_ScalarMultBase_noclamp_dev(void *q, const void *scalar, size_t n, void *stream);
+int ed25519_PointAdd_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
+int ed25519_PointAdd_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
+int ed25519_PointSub_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
+int ed25519_PointSub_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
 
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
