@@ -54,6 +54,18 @@ SIGNATURES = {
     "ed25519_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
     "ed25519_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ristretto255_IsValidPoint_batch": [_vp, _vp, _sz],
+    "ristretto255_IsValidPoint_dev": [_vp, _vp, _sz, _vp],
+    "ristretto255_FromHash_batch": [_vp, _vp, _sz],
+    "ristretto255_FromHash_dev": [_vp, _vp, _sz, _vp],
+    "ristretto255_ScalarMult_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_ScalarMult_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ristretto255_ScalarMultBase_batch": [_vp, _vp, _sz],
+    "ristretto255_ScalarMultBase_dev": [_vp, _vp, _sz, _vp],
+    "ristretto255_PointAdd_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ristretto255_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

@@ -194,6 +194,61 @@ def ed25519_PointSub(p, q):
     return _point_add(p, q, True)
 
 
+def ristretto255_IsValidPoint(point):
+    """n x ristretto255_IsValidPoint: int32[n], 1 where the 32 bytes decode by RFC 9496 section 4.3.1."""
+    point = _np(point, 32, "point")
+    ok = np.empty(point.shape[0], np.int32)
+    _lib.check(_lib.load().ristretto255_IsValidPoint_batch(_ptr(ok), _ptr(point), point.shape[0]), "ristretto255_IsValidPoint_batch")
+    return ok
+
+
+def ristretto255_FromHash(hash):
+    """n x ristretto255_FromHash: hash uint8[n, 64] -> uint8[n, 32], ENCODE(MAP(low half) + MAP(high half))."""
+    hash = _np(hash, 64, "hash")
+    p = np.empty((hash.shape[0], 32), np.uint8)
+    _lib.check(_lib.load().ristretto255_FromHash_batch(_ptr(p), _ptr(hash), hash.shape[0]), "ristretto255_FromHash_batch")
+    return p
+
+
+def ristretto255_ScalarMult(scalar, point):
+    """n x ristretto255_ScalarMult.  Returns (q uint8[n, 32], ok int32[n]): ok = 1 and q = ENCODE([e]P) where the point bytes decode
+    (the identity is 32 zero bytes with ok = 1), ok = 0 and 32 zero bytes where they do not; e is the scalar's low 255 bits.  The
+    scalar is not modified."""
+    scalar, point = _group_pairs(scalar, point, ("scalar", "point"))
+    n = scalar.shape[0]
+    q, ok = np.empty((n, 32), np.uint8), np.empty(n, np.int32)
+    _lib.check(_lib.load().ristretto255_ScalarMult_batch(_ptr(q), _ptr(ok), _ptr(scalar), _ptr(point), n), "ristretto255_ScalarMult_batch")
+    return q, ok
+
+
+def ristretto255_ScalarMultBase(scalar):
+    """n x ristretto255_ScalarMultBase: uint8[n, 32], ENCODE([e]B) for every scalar."""
+    scalar = _np(scalar, 32, "scalar")
+    q = np.empty((scalar.shape[0], 32), np.uint8)
+    _lib.check(_lib.load().ristretto255_ScalarMultBase_batch(_ptr(q), _ptr(scalar), scalar.shape[0]), "ristretto255_ScalarMultBase_batch")
+    return q
+
+
+def _rist_point_add(p, q, sub):
+    p, q = _group_pairs(p, q, ("p", "q"))
+    n = p.shape[0]
+    r, ok = np.empty((n, 32), np.uint8), np.empty(n, np.int32)
+    L = _lib.load()
+    fn = L.ristretto255_PointSub_batch if sub else L.ristretto255_PointAdd_batch
+    _lib.check(fn(_ptr(r), _ptr(ok), _ptr(p), _ptr(q), n), "ristretto255_PointSub_batch" if sub else "ristretto255_PointAdd_batch")
+    return r, ok
+
+
+def ristretto255_PointAdd(p, q):
+    """n x ristretto255_PointAdd.  Returns (r uint8[n, 32], ok int32[n]): ok = 1 and r = ENCODE(P + Q) where both decode, else zeros."""
+    return _rist_point_add(p, q, False)
+
+
+def ristretto255_PointSub(p, q):
+    """n x ristretto255_PointSub.  Returns (r uint8[n, 32], ok int32[n]): ok = 1 and r = ENCODE(P - Q) where both decode, else zeros."""
+    return _rist_point_add(p, q, True)
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -664,6 +719,63 @@ def ed25519_PointAdd_dev(r, ok, p, q):
 def ed25519_PointSub_dev(r, ok, p, q):
     """Device form of ed25519_PointSub: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
     _point_add_dev(r, ok, p, q, True)
+
+
+def ristretto255_IsValidPoint_dev(ok, point):
+    """Device form of ristretto255_IsValidPoint: point uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    import torch
+    n, d = point.shape[0], point.device
+    args = (_check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(point, 32, "point"))
+    with _on(point) as st:
+        _lib.check(_lib.load().ristretto255_IsValidPoint_dev(*args, n, st), "ristretto255_IsValidPoint_dev")
+
+
+def ristretto255_FromHash_dev(p, hash):
+    """Device form of ristretto255_FromHash: hash uint8[n, 64], p uint8[n, 32]; asynchronous on torch's current stream."""
+    n, d = hash.shape[0], hash.device
+    args = (_check(p, 32, "p", n, device=d), _check(hash, 64, "hash"))
+    with _on(hash) as st:
+        _lib.check(_lib.load().ristretto255_FromHash_dev(*args, n, st), "ristretto255_FromHash_dev")
+
+
+def ristretto255_ScalarMult_dev(q, ok, scalar, point):
+    """Device form of ristretto255_ScalarMult: scalar, point, q uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream.
+    The scalar is not written."""
+    import torch
+    n, d = scalar.shape[0], scalar.device
+    args = (_check(q, 32, "q", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(scalar, 32, "scalar"),
+            _check(point, 32, "point", n, device=d))
+    with _on(scalar) as st:
+        _lib.check(_lib.load().ristretto255_ScalarMult_dev(*args, n, st), "ristretto255_ScalarMult_dev")
+
+
+def ristretto255_ScalarMultBase_dev(q, scalar):
+    """Device form of ristretto255_ScalarMultBase: scalar, q uint8[n, 32]; asynchronous on torch's current stream."""
+    n, d = scalar.shape[0], scalar.device
+    args = (_check(q, 32, "q", n, device=d), _check(scalar, 32, "scalar"))
+    with _on(scalar) as st:
+        _lib.check(_lib.load().ristretto255_ScalarMultBase_dev(*args, n, st), "ristretto255_ScalarMultBase_dev")
+
+
+def _rist_point_add_dev(r, ok, p, q, sub):
+    import torch
+    L = _lib.load()
+    fn = L.ristretto255_PointSub_dev if sub else L.ristretto255_PointAdd_dev
+    n, d = p.shape[0], p.device
+    args = (_check(r, 32, "r", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(p, 32, "p"),
+            _check(q, 32, "q", n, device=d))
+    with _on(p) as st:
+        _lib.check(fn(*args, n, st), "ristretto255_PointSub_dev" if sub else "ristretto255_PointAdd_dev")
+
+
+def ristretto255_PointAdd_dev(r, ok, p, q):
+    """Device form of ristretto255_PointAdd: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    _rist_point_add_dev(r, ok, p, q, False)
+
+
+def ristretto255_PointSub_dev(r, ok, p, q):
+    """Device form of ristretto255_PointSub: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    _rist_point_add_dev(r, ok, p, q, True)
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

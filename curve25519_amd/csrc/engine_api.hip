@@ -772,6 +772,58 @@ int ed25519_PointSub_batch(unsigned char* r, int* ok, const unsigned char* p, co
     return point_add_batch(r, ok, p, q, n, true);
 }
 
+// ristretto255 (engine_ristretto.hip; csrc/ristretto255.cuh)
+int ristretto255_IsValidPoint_batch(int* ok, const unsigned char* point, size_t n)
+{
+    if (!ok || !point) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ point, nullptr, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_IsValidPoint_dev(d[1], d[0], c, st); });
+}
+
+int ristretto255_FromHash_batch(unsigned char* p, const unsigned char* hash, size_t n)
+{
+    if (!p || !hash) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ hash, nullptr, 64 }, Arr{ nullptr, p, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_FromHash_dev(d[1], d[0], c, st); });
+}
+
+int ristretto255_ScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
+{
+    if (!q || !ok || !scalar || !point) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ point, nullptr, 32 }, Arr{ nullptr, q, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_ScalarMult_dev(d[2], d[3], d[0], d[1], c, st); });
+}
+
+int ristretto255_ScalarMultBase_batch(unsigned char* q, const unsigned char* scalar, size_t n)
+{
+    if (!q || !scalar) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ nullptr, q, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_ScalarMultBase_dev(d[1], d[0], c, st); });
+}
+
+static int rist_point_add_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n, bool sub)
+{
+    if (!r || !ok || !p || !q) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    const auto call_dev = sub ? ristretto255_PointSub_dev : ristretto255_PointAdd_dev;
+    return run_batch(n, { Arr{ p, nullptr, 32 }, Arr{ q, nullptr, 32 }, Arr{ nullptr, r, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
+}
+
+int ristretto255_PointAdd_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
+{
+    return rist_point_add_batch(r, ok, p, q, n, false);
+}
+
+int ristretto255_PointSub_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
+{
+    return rist_point_add_batch(r, ok, p, q, n, true);
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

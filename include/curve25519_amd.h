@@ -54,7 +54,7 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
  * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there), SCALARMULT_WINDOW
- * (ed25519_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20).
+ * (ed25519_ScalarMult_* and ristretto255_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -309,6 +309,64 @@ int ed25519_PointAdd_batch(unsigned char *r, int *ok, const unsigned char *p, co
 int ed25519_PointAdd_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
 int ed25519_PointSub_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
 int ed25519_PointSub_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
+
+/* ristretto255 (RFC 9496): the prime-order group built on the same curve -- libsodium's crypto_core_ristretto255_* and
+ * crypto_scalarmult_ristretto255[_base], dalek's RistrettoPoint -- for OPRF / private set intersection, VOPRF and Privacy Pass
+ * issuance, Pedersen and Bulletproofs generators, Schnorrkel.  An element is 32 bytes; there is no cofactor, so no point has to be
+ * screened before it meets a secret scalar and no result reveals the scalar mod 8 (the _noclamp Edwards calls above need
+ * ed25519_ClassifyKey_* for that, a second walk as long as the multiplication).  Elements and scalars are n x 32 bytes, hash is
+ * n x 64 bytes, ok is n x int.
+ *   Decoding.  32 bytes decode exactly when DECODE of RFC 9496 section 4.3.1 succeeds: s < p, s even, the square root exists, t is
+ *     non-negative and y != 0.  There is no Edwards y / sign-bit form; the encodings the Edwards calls take are not ristretto255's.
+ *   ristretto255_IsValidPoint_*: ok[i] = 1 exactly when point[i] decodes, else 0 (crypto_core_ristretto255_is_valid_point).
+ *   ristretto255_FromHash_*: p[i] = ENCODE(MAP(low half) + MAP(high half)) of section 4.3.4 for the 64 bytes hash[i]: each half is
+ *     read little-endian with bit 255 masked and taken mod p (crypto_core_ristretto255_from_hash, dalek's from_uniform_bytes).  It
+ *     cannot fail: there is no ok array.
+ *   Scalar.  e is the low 255 bits of the 32-byte scalar: no clamp, bit 255 ignored as in the _noclamp Edwards calls.  The caller's
+ *     scalar bytes are never written.
+ *   ristretto255_ScalarMult_*: ok[i] = 1 exactly when point[i] decodes, and then q[i] = ENCODE([e]P); the identity encodes as 32 zero
+ *     bytes with ok = 1.  Otherwise ok[i] = 0 and q[i] is 32 zero bytes.  libsodium's crypto_scalarmult_ristretto255 additionally
+ *     returns -1 for an identity result; this call gives ok = 1 and the zero bytes (compare q with zero where that matters).
+ *   ristretto255_ScalarMultBase_*: q[i] = ENCODE([e]B) for every 32-byte scalar, over the wide comb (e = 0 mod L gives zero bytes;
+ *     libsodium's _base returns -1 there).
+ *   ristretto255_PointAdd_* / ristretto255_PointSub_*: ok[i] = 1 exactly when p[i] and q[i] both decode, and then
+ *     r[i] = ENCODE(P + Q) / ENCODE(P - Q); otherwise r[i] is 32 zero bytes and ok[i] = 0.
+ *   Every row of every output is written.  n == 0 returns 0; a null pointer is an argument error.  *_dev forms never synchronise
+ *   and take 16-byte aligned device pointers; *_batch forms stage through the calling thread's pipeline like their neighbours.
+ *   Secrecy.  The scalar and the 64 hash bytes are secret; point encodings are public.  No branch condition and no load or store
+ *     address derives from the scalar in ristretto255_ScalarMult_* (decoding and encoding included) or from the hash bytes in
+ *     ristretto255_FromHash_*: every comparison of the square-root step, the rotation and the negations of the encoding and the
+ *     selections of the map are masks.  ristretto255_ScalarMultBase_* fetches the base comb's rows by secret index, exactly as
+ *     ed25519_ScalarMultBase_*, key pairs and signing do.
+ * One lane per element at every n (no per-wave or four-lane form; c25519_amd_last_shape is not written) and ONE kernel per call: the
+ * encoding's inverse square root cannot be shared between elements as an inversion can, so it runs in the lane (one x^((p-5)/8)
+ * chain, 254 squarings and 11 products) and no call leases scratch.  The walk's and the comb's last additions do not form T, which
+ * the encoding reads: the point is re-formed as (X Z, Y Z, Z^2, X Y) in front of it (three products and a squaring), and the walk
+ * stays as the Edwards calls run it.  ristretto255_ScalarMult_* is decode, the Edwards calls' variable-base walk (tunable
+ * SCALARMULT_WINDOW: W = 2, 3 or 4) and encode in one kernel: the walk's products plus two chains.  FromHash is three chains,
+ * ScalarMultBase the comb plus one chain, PointAdd / PointSub three chains, IsValidPoint one.
+ * Measured (profiles/ristretto_rate.txt, interleaved rounds, the Edwards call of the same build on the same n beside each): at 2^20
+ * ScalarMult_dev runs 86.2 M/s at W = 2 (12.16 ms), 82.5 at W = 3, 80.7 at W = 4, against 91.9 / 86.0 / 87.3 M/s for
+ * ed25519_ScalarMult_noclamp_dev: 0.94 x / 0.96 x / 0.93 x.  The counts said so: a chain measures 0.75-0.80 ms per 2^20 elements
+ * (IsValidPoint_dev, one chain and a dozen products: 0.77 ms, 1.36 G/s), the Edwards call already pays one for its own decoding, and
+ * the second chain with the re-formed point replaces that call's share of the batch inversion.  W = 2 wins by 0.55 ms where the rounds
+ * spread over 0.02 ms and is the built-in width, as for the Edwards calls.  ScalarMultBase_dev: 680 M/s (1.54 ms) against 1.31 G/s for
+ * ed25519_ScalarMultBase_noclamp_dev, 0.52 x: the chain is half of the call, as expected.  PointAdd_dev / PointSub_dev: 437-445 M/s
+ * (2.36-2.40 ms, 0.67-0.68 x ed25519_PointAdd_dev's 656 M/s); FromHash_dev: 434 M/s (2.41 ms, three chains).  Up to 2^16 elements a
+ * call is one lane's latency: 0.88-0.89 ms for ScalarMult at W = 2 (0.79-0.80 at W = 3), 0.12-0.13 ms for ScalarMultBase, 0.19-0.20 ms
+ * for PointAdd / PointSub / FromHash, 0.07 ms for IsValidPoint; a call of ONE element 0.88-1.02 ms / 0.13-0.15 / 0.19-0.22 / 0.07-0.08 ms. */
+int ristretto255_IsValidPoint_batch(int *ok, const unsigned char *point, size_t n);
+int ristretto255_IsValidPoint_dev(void *ok, const void *point, size_t n, void *stream);
+int ristretto255_FromHash_batch(unsigned char *p, const unsigned char *hash /* n x 64 */, size_t n);
+int ristretto255_FromHash_dev(void *p, const void *hash, size_t n, void *stream);
+int ristretto255_ScalarMult_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t n);
+int ristretto255_ScalarMult_dev(void *q, void *ok, const void *scalar, const void *point, size_t n, void *stream);
+int ristretto255_ScalarMultBase_batch(unsigned char *q, const unsigned char *scalar, size_t n);
+int ristretto255_ScalarMultBase_dev(void *q, const void *scalar, size_t n, void *stream);
+int ristretto255_PointAdd_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
+int ristretto255_PointAdd_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
+int ristretto255_PointSub_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
+int ristretto255_PointSub_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
 
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its

@@ -621,6 +621,97 @@ def main():
     need(all(num[i] <= R[i] and den[i] <= R[i] for i in range(10)), "key conversion: 1 + y / 1 - y not reduced")
     to_words(mul(num, R, "key u"), "key u to_words")
     print("key classification walk [L]A and conversion to X25519: ok")
+    # ---- ristretto255.cuh: SQRT_RATIO_M1, DECODE, ENCODE and the Elligator MAP (RFC 9496) ----
+    def reduced(v, what):
+        need(all(v[i] <= R[i] for i in range(10)), f"{what} not reduced")
+        return v
+
+    def rist_cneg(a, what):                                  # fe_neg, fe_select, fe_carry32
+        return reduced(carry32(select(neg(a, f"{what} neg"), a), what), what)
+
+    def rist_abs(a, what):
+        to_words(a, f"{what} parity")
+        return rist_cneg(a, what)
+
+    def rist_sqrt_ratio(u, v, unit_u, what):                 # u, v reduced
+        b = sqr(v, f"{what} v^2")
+        a = mul(b, v, f"{what} v^3")
+        if not unit_u:
+            a = mul(a, u, f"{what} u v^3")
+        b = mul(a, sqr(b, f"{what} v^4"), f"{what} u v^7")
+        chain250(b, R)
+        r = mul(R, a, f"{what} r")
+        check = mul(sqr(r, f"{what} r^2"), v, f"{what} check")
+        ui = CANON if unit_u else mul(u, CANON, f"{what} u sqrt(-1)")
+        to_words(sub(check, u, f"{what} check - u"), f"{what} correct")
+        to_words(add(check, u), f"{what} flipped")
+        to_words(add(check, ui), f"{what} flipped_i")
+        return rist_abs(select(mul(r, CANON, f"{what} r sqrt(-1)"), r), f"{what} |r|")
+
+    def rist_decode():
+        s = FROM_WORDS
+        ss = sqr(s, "decode s^2")
+        u1 = reduced(carry32(sub(ONE, ss, "decode 1 - ss")), "decode u1")
+        u2 = add(ss, ONE)
+        u2s = sqr(u2, "decode u2^2")
+        t = carry32(add(mul(sqr(u1, "decode u1^2"), CANON, "decode d u1^2"), u2s))
+        v = reduced(carry32(neg(t, "decode -t")), "decode v")
+        inv = rist_sqrt_ratio(ONE, mul(v, u2s, "decode v u2^2"), True, "decode sqrt")
+        dx = mul(inv, u2, "decode den_x")
+        dy = mul(mul(inv, dx, "decode inv den_x"), v, "decode den_y")
+        X = rist_abs(mul(add(s, s), dx, "decode 2 s den_x"), "decode x")
+        Y = mul(u1, dy, "decode y")
+        to_words(mul(X, Y, "decode t"), "decode t parity")
+        to_words(Y, "decode y == 0")
+        return rist_cneg(X, "decode -x"), reduced(Y, "decode y")
+
+    def rist_encode(X, Y, Z, T, has_t):
+        if not has_t:
+            X, Y, T, Z = mul(X, Z, "encode XZ"), mul(Y, Z, "encode YZ"), mul(X, Y, "encode XY"), sqr(Z, "encode Z^2")
+        u1 = mul(sub(Z, Y, "encode Z - Y"), add(Z, Y), "encode u1")
+        u2 = mul(X, Y, "encode u2")
+        inv = rist_sqrt_ratio(ONE, mul(u1, sqr(u2, "encode u2^2"), "encode u1 u2^2"), True, "encode sqrt")
+        d1, d2 = mul(inv, u1, "encode den1"), mul(inv, u2, "encode den2")
+        zi = mul(mul(d1, d2, "encode den1 den2"), T, "encode z_inv")
+        to_words(mul(T, zi, "encode t z_inv"), "encode rotate")
+        x = select(mul(Y, CANON, "encode iy"), X)
+        y = select(mul(X, CANON, "encode ix"), Y)
+        di = select(mul(d1, CANON, "encode enchanted"), d2)
+        to_words(mul(x, zi, "encode x z_inv"), "encode neg y")
+        y = rist_cneg(y, "encode -y")
+        to_words(mul(sub(Z, y, "encode Z - y"), di, "encode s"), "encode s to_words")
+
+    def rist_map(t):
+        r = mul(sqr(t, "map t^2"), CANON, "map r")
+        u = mul(add(r, ONE), CANON, "map u")
+        a = neg(add(mul(r, CANON, "map r d"), ONE), "map -1 - r d")
+        v = mul(a, add(r, CANON), "map v")
+        s = rist_sqrt_ratio(u, v, False, "map sqrt")
+        sp = rist_cneg(mul(s, t, "map s t"), "map s'")
+        to_words(mul(s, t, "map s t"), "map s t parity")
+        s = select(s, sp)
+        c = select(neg(ONE, "map -1"), r)
+        n = mul(mul(sub(r, ONE, "map r - 1"), c, "map c (r - 1)"), CANON, "map c (r - 1)(d - 1)^2")
+        n = sub(n, v, "map N")
+        w0 = mul(add(s, s), v, "map w0")
+        w1 = mul(n, CANON, "map w1")
+        w3 = sqr(s, "map s^2")
+        w2 = sub(ONE, w3, "map w2")
+        w3 = add(w3, ONE)
+        return (reduced(mul(w0, w3, "map X"), "map X"), reduced(mul(w2, w1, "map Y"), "map Y"), reduced(mul(w1, w3, "map Z"), "map Z"),
+                reduced(mul(w2, w0, "map T"), "map T"))
+
+    x, y = rist_decode()
+    for v in ge_add(x, y, ONE, mul(x, y, "rist add T"), carry32(add(y, x)), carry32(sub(y, x, "rist add Y-X")),
+                    mul(mul(x, y, "rist add xy"), CANON, "rist add 2dxy"), None):
+        reduced(v, "ristretto255 PointAdd")
+    rist_encode(R, R, R, R, True)                            # PointAdd, FromHash: the addition's own T
+    rist_encode(R, R, R, R, False)                           # ScalarMult, ScalarMultBase: re-formed from the walk's (X, Y, Z)
+    P1 = rist_map(FROM_WORDS)
+    for v in ge_add(*P1, carry32(add(P1[1], P1[0])), carry32(sub(P1[1], P1[0], "rist pe ymx")), mul(P1[3], CANON, "rist pe t2d"),
+                    carry32(add(P1[2], P1[2]))):
+        reduced(v, "ristretto255 FromHash addition")
+    print("ristretto255 square-root step, decode, encode (with T and re-formed), Elligator map: ok")
     quad_section(R)
     print("quad25519 ladder step, addition, doubling, batch-inversion exchange: ok")
     small = coop_section(R)
