@@ -66,6 +66,24 @@ SIGNATURES = {
     "ristretto255_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
     "ristretto255_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
     "ristretto255_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarReduce_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarReduce_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_ScalarAdd_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarAdd_dev": [_vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarSub_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarSub_dev": [_vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarMul_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarMul_dev": [_vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarNegate_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarNegate_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_ScalarComplement_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarComplement_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_ScalarMulAdd_batch": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarMulAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarInvert_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarInvert_dev": [_vp, _vp, _vp, _sz, _vp],
+    "ed25519_ScalarIsCanonical_batch": [_vp, _vp, _sz],
+    "ed25519_ScalarIsCanonical_dev": [_vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

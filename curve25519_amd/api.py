@@ -249,6 +249,74 @@ def ristretto255_PointSub(p, q):
     return _rist_point_add(p, q, True)
 
 
+def _scalar_rows(arrays, names, width=32):
+    arrays = [_np(a, width, name) for a, name in zip(arrays, names)]
+    if any(a.shape[0] != arrays[0].shape[0] for a in arrays):
+        raise ValueError(f"{', '.join(names)} must have the same number of rows")
+    return arrays
+
+
+def _scalar_call(name, arrays, names, width=32):
+    arrays = _scalar_rows(arrays, names, width)
+    n = arrays[0].shape[0]
+    r = np.empty((n, 32), np.uint8)
+    _lib.check(getattr(_lib.load(), name)(_ptr(r), *[_ptr(a) for a in arrays], n), name)
+    return r
+
+
+def ed25519_ScalarReduce(s):
+    """n x ed25519_ScalarReduce: s uint8[n, 64] -> uint8[n, 32], the 512-bit value mod L."""
+    return _scalar_call("ed25519_ScalarReduce_batch", (s,), ("s",), 64)
+
+
+def ed25519_ScalarAdd(x, y):
+    """n x ed25519_ScalarAdd: uint8[n, 32], x + y mod L (canonical; the inputs may be any 32-byte values)."""
+    return _scalar_call("ed25519_ScalarAdd_batch", (x, y), ("x", "y"))
+
+
+def ed25519_ScalarSub(x, y):
+    """n x ed25519_ScalarSub: uint8[n, 32], x - y mod L."""
+    return _scalar_call("ed25519_ScalarSub_batch", (x, y), ("x", "y"))
+
+
+def ed25519_ScalarMul(x, y):
+    """n x ed25519_ScalarMul: uint8[n, 32], x y mod L."""
+    return _scalar_call("ed25519_ScalarMul_batch", (x, y), ("x", "y"))
+
+
+def ed25519_ScalarNegate(s):
+    """n x ed25519_ScalarNegate: uint8[n, 32], -s mod L."""
+    return _scalar_call("ed25519_ScalarNegate_batch", (s,), ("s",))
+
+
+def ed25519_ScalarComplement(s):
+    """n x ed25519_ScalarComplement: uint8[n, 32], 1 - s mod L."""
+    return _scalar_call("ed25519_ScalarComplement_batch", (s,), ("s",))
+
+
+def ed25519_ScalarMulAdd(a, b, c):
+    """n x ed25519_ScalarMulAdd: uint8[n, 32], a b + c mod L."""
+    return _scalar_call("ed25519_ScalarMulAdd_batch", (a, b, c), ("a", "b", "c"))
+
+
+def ed25519_ScalarInvert(s):
+    """n x ed25519_ScalarInvert.  Returns (recip uint8[n, 32], ok int32[n]): ok = 1 and recip = 1 / s mod L where s mod L != 0, ok = 0
+    and 32 zero bytes where it is zero (s = L included: zero is judged after reduction)."""
+    s = _np(s, 32, "s")
+    n = s.shape[0]
+    recip, ok = np.empty((n, 32), np.uint8), np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_ScalarInvert_batch(_ptr(recip), _ptr(ok), _ptr(s), n), "ed25519_ScalarInvert_batch")
+    return recip, ok
+
+
+def ed25519_ScalarIsCanonical(s):
+    """n x ed25519_ScalarIsCanonical: int32[n], 1 where the 32 bytes are below L."""
+    s = _np(s, 32, "s")
+    ok = np.empty(s.shape[0], np.int32)
+    _lib.check(_lib.load().ed25519_ScalarIsCanonical_batch(_ptr(ok), _ptr(s), s.shape[0]), "ed25519_ScalarIsCanonical_batch")
+    return ok
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -776,6 +844,67 @@ def ristretto255_PointAdd_dev(r, ok, p, q):
 def ristretto255_PointSub_dev(r, ok, p, q):
     """Device form of ristretto255_PointSub: p, q, r uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
     _rist_point_add_dev(r, ok, p, q, True)
+
+
+def _scalar_call_dev(name, r, inputs, names, width=32):
+    n, d = inputs[0].shape[0], inputs[0].device
+    args = [_check(r, 32, "r", n, device=d)] + [_check(t, width, nm, n, device=d) for t, nm in zip(inputs, names)]
+    with _on(inputs[0]) as st:
+        _lib.check(getattr(_lib.load(), name)(*args, n, st), name)
+
+
+def ed25519_ScalarReduce_dev(r, s):
+    """Device form of ed25519_ScalarReduce: s uint8[n, 64], r uint8[n, 32]; asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarReduce_dev", r, (s,), ("s",), 64)
+
+
+def ed25519_ScalarAdd_dev(z, x, y):
+    """Device form of ed25519_ScalarAdd: x, y, z uint8[n, 32] (z may be x or y); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarAdd_dev", z, (x, y), ("x", "y"))
+
+
+def ed25519_ScalarSub_dev(z, x, y):
+    """Device form of ed25519_ScalarSub: x, y, z uint8[n, 32] (z may be x or y); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarSub_dev", z, (x, y), ("x", "y"))
+
+
+def ed25519_ScalarMul_dev(z, x, y):
+    """Device form of ed25519_ScalarMul: x, y, z uint8[n, 32] (z may be x or y); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarMul_dev", z, (x, y), ("x", "y"))
+
+
+def ed25519_ScalarNegate_dev(r, s):
+    """Device form of ed25519_ScalarNegate: s, r uint8[n, 32] (r may be s); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarNegate_dev", r, (s,), ("s",))
+
+
+def ed25519_ScalarComplement_dev(r, s):
+    """Device form of ed25519_ScalarComplement: s, r uint8[n, 32] (r may be s); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarComplement_dev", r, (s,), ("s",))
+
+
+def ed25519_ScalarMulAdd_dev(r, a, b, c):
+    """Device form of ed25519_ScalarMulAdd: a, b, c, r uint8[n, 32] (r may be one of them); asynchronous on torch's current stream."""
+    _scalar_call_dev("ed25519_ScalarMulAdd_dev", r, (a, b, c), ("a", "b", "c"))
+
+
+def ed25519_ScalarInvert_dev(recip, ok, s):
+    """Device form of ed25519_ScalarInvert: s, recip uint8[n, 32] (recip may be s), ok int32[n, 1]; asynchronous on torch's current
+    stream."""
+    import torch
+    n, d = s.shape[0], s.device
+    args = (_check(recip, 32, "recip", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(s, 32, "s"))
+    with _on(s) as st:
+        _lib.check(_lib.load().ed25519_ScalarInvert_dev(*args, n, st), "ed25519_ScalarInvert_dev")
+
+
+def ed25519_ScalarIsCanonical_dev(ok, s):
+    """Device form of ed25519_ScalarIsCanonical: s uint8[n, 32], ok int32[n, 1]; asynchronous on torch's current stream."""
+    import torch
+    n, d = s.shape[0], s.device
+    args = (_check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(s, 32, "s"))
+    with _on(s) as st:
+        _lib.check(_lib.load().ed25519_ScalarIsCanonical_dev(*args, n, st), "ed25519_ScalarIsCanonical_dev")
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

@@ -824,6 +824,57 @@ int ristretto255_PointSub_batch(unsigned char* r, int* ok, const unsigned char* 
     return rist_point_add_batch(r, ok, p, q, n, true);
 }
 
+// the scalar field mod L (engine_scalar.hip; csrc/sc_invert.cuh)
+typedef int (*sc_unary_dev_fn)(void*, const void*, size_t, void*);
+typedef int (*sc_binary_dev_fn)(void*, const void*, const void*, size_t, void*);
+
+static int sc_unary_batch(unsigned char* r, const unsigned char* s, size_t in_bytes, size_t n, sc_unary_dev_fn call_dev)
+{
+    if (!r || !s) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ s, nullptr, in_bytes }, Arr{ nullptr, r, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], c, st); });
+}
+
+static int sc_binary_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n, sc_binary_dev_fn call_dev)
+{
+    if (!z || !x || !y) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ x, nullptr, 32 }, Arr{ y, nullptr, 32 }, Arr{ nullptr, z, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[0], d[1], c, st); });
+}
+
+int ed25519_ScalarReduce_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 64, n, ed25519_ScalarReduce_dev); }
+int ed25519_ScalarNegate_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 32, n, ed25519_ScalarNegate_dev); }
+int ed25519_ScalarComplement_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 32, n, ed25519_ScalarComplement_dev); }
+int ed25519_ScalarAdd_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarAdd_dev); }
+int ed25519_ScalarSub_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarSub_dev); }
+int ed25519_ScalarMul_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarMul_dev); }
+
+int ed25519_ScalarMulAdd_batch(unsigned char* r, const unsigned char* a, const unsigned char* b, const unsigned char* c, size_t n)
+{
+    if (!r || !a || !b || !c) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ a, nullptr, 32 }, Arr{ b, nullptr, 32 }, Arr{ c, nullptr, 32 }, Arr{ nullptr, r, 32 } },
+                     [&](void** d, size_t cnt, size_t, hipStream_t st) -> int { return ed25519_ScalarMulAdd_dev(d[3], d[0], d[1], d[2], cnt, st); });
+}
+
+int ed25519_ScalarInvert_batch(unsigned char* recip, int* ok, const unsigned char* s, size_t n)
+{
+    if (!recip || !ok || !s) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ s, nullptr, 32 }, Arr{ nullptr, recip, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_ScalarInvert_dev(d[1], d[2], d[0], c, st); });
+}
+
+int ed25519_ScalarIsCanonical_batch(int* ok, const unsigned char* s, size_t n)
+{
+    if (!ok || !s) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ s, nullptr, 32 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_ScalarIsCanonical_dev(d[1], d[0], c, st); });
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

@@ -54,7 +54,8 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * default 98304; 0 = never), PEER_INDEXED_MIN (curve25519_dh_CreateSharedKey_indexed_*: the smallest batch that walks the peer
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
  * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there), SCALARMULT_WINDOW
- * (ed25519_ScalarMult_* and ristretto255_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20).
+ * (ed25519_ScalarMult_* and ristretto255_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20),
+ * SC_INVERT_K (ed25519_ScalarInvert_*: elements per inverting lane, 1, 2, 4, 8 or 16; anything else: the built-in choice by n, see there).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -367,6 +368,60 @@ int ristretto255_PointAdd_batch(unsigned char *r, int *ok, const unsigned char *
 int ristretto255_PointAdd_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
 int ristretto255_PointSub_batch(unsigned char *r, int *ok, const unsigned char *p, const unsigned char *q, size_t n);
 int ristretto255_PointSub_dev(void *r, void *ok, const void *p, const void *q, size_t n, void *stream);
+
+/* The scalar field: arithmetic mod L = 2^252 + 27742317777372353535851937790883648493, the order of the base point -- libsodium's
+ * crypto_core_ed25519_scalar_* and crypto_core_ristretto255_scalar_* (the same functions under two names there, ONE set of names
+ * here), ref10's sc25519_muladd, dalek's Scalar -- so that a protocol over the group calls above stays on the device: an OPRF
+ * evaluation is unblinded by 1/r, a Schnorr or DLEQ response is k + c x, a hash becomes a scalar by a 64-byte reduction.
+ * A scalar is 32 little-endian bytes per element (ScalarReduce's input: 64); ok is n x int.
+ *   Inputs.  Every input may be ANY 32-byte value, not only a reduced one: it stands for its value mod L.  (libsodium asks for
+ *     reduced inputs in _scalar_mul; there is no such condition here.)
+ *   Outputs.  Every output is the canonical representative in [0, L).
+ *   ed25519_ScalarReduce_*: r[i] = s[i] mod L for the 512-bit s[i] (_scalar_reduce).
+ *   ed25519_ScalarAdd_* / _ScalarSub_* / _ScalarMul_*: z[i] = x[i] + y[i] / x[i] - y[i] / x[i] y[i] (_scalar_add / _sub / _mul).
+ *   ed25519_ScalarNegate_*: r[i] = -s[i] (_scalar_negate).  ed25519_ScalarComplement_*: r[i] = 1 - s[i] (_scalar_complement).
+ *   ed25519_ScalarMulAdd_*: r[i] = a[i] b[i] + c[i] (sc25519_muladd).
+ *   ed25519_ScalarInvert_*: ok[i] = 1 and recip[i] = 1 / s[i] exactly when s[i] mod L != 0; otherwise recip[i] is 32 zero bytes and
+ *     ok[i] = 0 (_scalar_invert).  The one difference from libsodium: zero is judged AFTER reduction, so s = L (or any multiple of L)
+ *     gives ok = 0; libsodium compares the raw bytes with zero and returns 0 for s = L.
+ *   ed25519_ScalarIsCanonical_*: ok[i] = 1 exactly when s[i] < L (dalek's Scalar::from_canonical_bytes).
+ *   Inputs are never written.  An output buffer may be exactly an input buffer (in place: same pointer, same n); any other overlap
+ *   between an output and another argument is undefined.  Every row of every output is written.
+ *   n == 0 returns 0, with or without a device; a null pointer is an argument error.  Without a device every other call fails with
+ *   an error code and c25519_amd_last_error()'s text: there is no CPU result.  *_dev forms never synchronise and take 16-byte
+ *   aligned device pointers; *_batch forms stage through the calling thread's pipeline like their neighbours.
+ *   c25519_amd_last_shape is not written.
+ *   Secrecy.  Every scalar is secret.  No branch condition and no load or store address derives from a scalar's value in any of these
+ *     calls: reductions, the zero test of Invert and its forced-zero output are masks; the only decisions are on the element index.
+ * One lane per element at every n, one kernel per call, no scratch leased.  The element-wise calls move 96-160 bytes per element
+ * behind a few hundred instructions.  ed25519_ScalarInvert_* is Bernstein-Yang division steps mod L (csrc/sc_invert.cuh: the 20
+ * batches of 30 steps of the field inversion, with the cofactor update and the normalisation written for L), ~16 000 instructions
+ * where a Fermat chain over the scalar product would be ~85 000, shared between the K elements of a lane by Montgomery's trick:
+ * three scalar products per element plus one inversion per lane.  Tunable SC_INVERT_K: 1, 2, 4, 8 or 16; anything else is the
+ * built-in choice, the smallest K that fits the lanes into one wave per SIMD (65 536 lanes), at most 8.
+ * Measured (tools/scalar_rate.py, profiles/scalar_rate.txt; interleaved rounds, 20 launches back to back per figure): up to 2^16
+ * elements ScalarInvert_dev is one lane's inversion, 0.027-0.030 ms a call at K = 1 (K = 2 / 4 / 8 / 16: 0.031-0.033 / 0.041 / 0.060 /
+ * 0.097 ms); 2^17 takes 0.035 ms at K = 2, 2^18 0.043 ms at K = 4, 2^19 0.066 ms at K = 8, 2^20 0.099 ms at K = 8 (10.6 G/s; K = 16:
+ * 0.111, K = 4: 0.132, K = 1: 0.373 ms) -- at each size the built-in K is the fastest by more than the rounds' spread (0.000-0.003 ms).
+ * At 2^20 ScalarMul_dev takes 0.020 ms (52 G/s), ScalarMulAdd_dev 0.024 ms (44 G/s), ScalarReduce_dev 0.017 ms (62 G/s). */
+int ed25519_ScalarReduce_batch(unsigned char *r, const unsigned char *s /* n x 64 */, size_t n);
+int ed25519_ScalarReduce_dev(void *r, const void *s, size_t n, void *stream);
+int ed25519_ScalarAdd_batch(unsigned char *z, const unsigned char *x, const unsigned char *y, size_t n);
+int ed25519_ScalarAdd_dev(void *z, const void *x, const void *y, size_t n, void *stream);
+int ed25519_ScalarSub_batch(unsigned char *z, const unsigned char *x, const unsigned char *y, size_t n);
+int ed25519_ScalarSub_dev(void *z, const void *x, const void *y, size_t n, void *stream);
+int ed25519_ScalarMul_batch(unsigned char *z, const unsigned char *x, const unsigned char *y, size_t n);
+int ed25519_ScalarMul_dev(void *z, const void *x, const void *y, size_t n, void *stream);
+int ed25519_ScalarNegate_batch(unsigned char *r, const unsigned char *s, size_t n);
+int ed25519_ScalarNegate_dev(void *r, const void *s, size_t n, void *stream);
+int ed25519_ScalarComplement_batch(unsigned char *r, const unsigned char *s, size_t n);
+int ed25519_ScalarComplement_dev(void *r, const void *s, size_t n, void *stream);
+int ed25519_ScalarMulAdd_batch(unsigned char *r, const unsigned char *a, const unsigned char *b, const unsigned char *c, size_t n);
+int ed25519_ScalarMulAdd_dev(void *r, const void *a, const void *b, const void *c, size_t n, void *stream);
+int ed25519_ScalarInvert_batch(unsigned char *recip, int *ok, const unsigned char *s, size_t n);
+int ed25519_ScalarInvert_dev(void *recip, void *ok, const void *s, size_t n, void *stream);
+int ed25519_ScalarIsCanonical_batch(int *ok, const unsigned char *s, size_t n);
+int ed25519_ScalarIsCanonical_dev(void *ok, const void *s, size_t n, void *stream);
 
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its

@@ -112,6 +112,15 @@ assert D_MINUS_ONE_SQ == 4044083434630853685810104246932319082624839914623870835
 assert INVSQRT_A_MINUS_D ** 2 * (-1 - d) % p == 1 and SQRT_AD_MINUS_ONE ** 2 % p == (-d - 1) % p and SQRT_AD_MINUS_ONE & 1
 
 
+# inversion mod L by division steps (sc_invert.cuh): L in the 30-bit limbs of safegcd25519.cuh and L^-1 mod 2^30.  L = 2^252 + c with
+# c < 2^125, so limbs 0..4 hold c, limbs 5..7 are zero and limb 8 is 2^(252 - 240): six multiply-adds per number and batch.
+L_LIMBS30 = [(L >> (30 * i)) & (2**30 - 1) for i in range(9)]
+L_INV30 = pow(L, -1, 2**30)
+assert sum(v << (30 * i) for i, v in enumerate(L_LIMBS30)) == L and L >> 270 == 0
+assert all(L_LIMBS30[i] for i in (0, 1, 2, 3, 4)) and L_LIMBS30[5:8] == [0, 0, 0] and L_LIMBS30[8] == 1 << 12
+assert L * L_INV30 % 2**30 == 1 and L_INV30 == 0x2DAB81E5
+
+
 def words(v):
     return ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xFFFFFFFF) for i in range(8))
 
@@ -141,6 +150,9 @@ out.append("__device__ constexpr uint32_t K_MINUS_R[5] = { %s };" % ", ".join(
 out.append("// multiples of L that keep sc_reduce512's two folds non-negative: L << 134 (13 words, > 2^385) and L << 9 (9 words, > 2^260)")
 out.append("__device__ constexpr uint32_t K_L_SHL134[13] = { %s };" % ", ".join("0x%08xu" % (((L << 134) >> (32 * i)) & 0xFFFFFFFF) for i in range(13)))
 out.append("__device__ constexpr uint32_t K_L_SHL9[9] = { %s };" % ", ".join("0x%08xu" % (((L << 9) >> (32 * i)) & 0xFFFFFFFF) for i in range(9)))
+out.append("// L as nine 30-bit limbs (limbs 5..7 are zero, limb 8 is 2^12) and L^-1 mod 2^30: the modulus of sc_invert.cuh's division steps")
+out.append("__device__ constexpr int32_t K_L_LIMBS30[9] = { %s };" % ", ".join("0x%08x" % v for v in L_LIMBS30))
+out.append("constexpr uint32_t K_L_INV30 = 0x%08xu;" % L_INV30)
 out.append("// p = 2^255 - 19, and the 255-bit y whose y mod p is the y of a point of small order: 0, 1, the two y of the points of")
 out.append("// order 8, p - 1, p, p + 1 (strict25519.cuh)")
 out.append("__device__ constexpr uint32_t K_P[8] = { %s };" % words(p))
