@@ -84,6 +84,18 @@ SIGNATURES = {
     "ed25519_ScalarInvert_dev": [_vp, _vp, _vp, _sz, _vp],
     "ed25519_ScalarIsCanonical_batch": [_vp, _vp, _sz],
     "ed25519_ScalarIsCanonical_dev": [_vp, _vp, _sz, _vp],
+    "c25519_ExpandMessageXmd_batch": [_vp, _vp, _sz, _vp, _sz, _sz, _sz],
+    "c25519_ExpandMessageXmd_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp],
+    "ed25519_MapToCurve_batch": [_vp, _vp, _sz],
+    "ed25519_MapToCurve_dev": [_vp, _vp, _sz, _vp],
+    "ed25519_HashToCurve_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_HashToCurve_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
+    "ed25519_EncodeToCurve_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_EncodeToCurve_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
+    "ristretto255_HashToGroup_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ristretto255_HashToGroup_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
+    "ed25519_HashToScalar_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_HashToScalar_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

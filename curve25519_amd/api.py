@@ -317,6 +317,64 @@ def ed25519_ScalarIsCanonical(s):
     return ok
 
 
+def _h2c_args(msg, dst):
+    """(msg uint8[n, msg_size], dst as a bytes buffer): the rows of a hashing call and its domain separation tag"""
+    msg = np.ascontiguousarray(msg, dtype=np.uint8)
+    if msg.ndim != 2:
+        raise ValueError(f"msg must have shape (n, msg_size), got {msg.shape}")
+    return msg, bytes(dst)
+
+
+def _h2c_call(name, msg, dst):
+    msg, dst = _h2c_args(msg, dst)
+    n, msg_size = msg.shape
+    out = np.empty((n, 32), np.uint8)
+    _lib.check(getattr(_lib.load(), name)(_ptr(out), _ptr(msg) if msg_size else None, msg_size, dst, len(dst), n), name)
+    return out
+
+
+def c25519_ExpandMessageXmd(msg, dst, len_in_bytes):
+    """n x expand_message_xmd over SHA-512 (RFC 9380 section 5.3.1): msg uint8[n, msg_size], dst 1 .. 255 bytes ->
+    uint8[n, len_in_bytes], 1 <= len_in_bytes <= 16320."""
+    msg, dst = _h2c_args(msg, dst)
+    n, msg_size = msg.shape
+    out = np.empty((n, max(int(len_in_bytes), 0)), np.uint8)
+    _lib.check(_lib.load().c25519_ExpandMessageXmd_batch(_ptr(out), _ptr(msg) if msg_size else None, msg_size, dst, len(dst),
+                                                         int(len_in_bytes), n), "c25519_ExpandMessageXmd_batch")
+    return out
+
+
+def ed25519_MapToCurve(u):
+    """n x map_to_curve_elligator2_edwards25519 (RFC 9380 section 6.8.2): u uint8[n, 32] (little-endian, bit 255 masked, mod p) ->
+    the Ed25519 encodings uint8[n, 32]; no cofactor cleared, u = 0 gives the identity."""
+    u = _np(u, 32, "u")
+    p = np.empty((u.shape[0], 32), np.uint8)
+    _lib.check(_lib.load().ed25519_MapToCurve_batch(_ptr(p), _ptr(u), u.shape[0]), "ed25519_MapToCurve_batch")
+    return p
+
+
+def ed25519_HashToCurve(msg, dst):
+    """n x edwards25519_XMD:SHA-512_ELL2_RO_ under the DST dst: msg uint8[n, msg_size] -> the Ed25519 encodings uint8[n, 32]."""
+    return _h2c_call("ed25519_HashToCurve_batch", msg, dst)
+
+
+def ed25519_EncodeToCurve(msg, dst):
+    """n x edwards25519_XMD:SHA-512_ELL2_NU_ under the DST dst: msg uint8[n, msg_size] -> the Ed25519 encodings uint8[n, 32]."""
+    return _h2c_call("ed25519_EncodeToCurve_batch", msg, dst)
+
+
+def ristretto255_HashToGroup(msg, dst):
+    """n x hash_to_ristretto255 (RFC 9380 appendix B; RFC 9497's HashToGroup with dst = "HashToGroup-" || contextString):
+    msg uint8[n, msg_size] -> uint8[n, 32]."""
+    return _h2c_call("ristretto255_HashToGroup_batch", msg, dst)
+
+
+def ed25519_HashToScalar(msg, dst):
+    """n x RFC 9497's HashToScalar for ristretto255 (dst = "HashToScalar-" || contextString): msg uint8[n, msg_size] -> the
+    canonical scalars uint8[n, 32], 64 expander bytes little-endian mod L."""
+    return _h2c_call("ed25519_HashToScalar_batch", msg, dst)
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -905,6 +963,49 @@ def ed25519_ScalarIsCanonical_dev(ok, s):
     args = (_check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(s, 32, "s"))
     with _on(s) as st:
         _lib.check(_lib.load().ed25519_ScalarIsCanonical_dev(*args, n, st), "ed25519_ScalarIsCanonical_dev")
+
+
+def _h2c_call_dev(name, out, width, msg, dst, *extra):
+    n, d = msg.shape[0], msg.device
+    dst = bytes(dst)
+    args = (_check(out, width, "out", n, device=d), _check(msg, None, "msg") if msg.shape[1] else None)
+    with _on(msg) as st:
+        _lib.check(getattr(_lib.load(), name)(*args, msg.shape[1], dst, len(dst), *extra, n, st), name)
+
+
+def c25519_ExpandMessageXmd_dev(out, msg, dst):
+    """Device form of c25519_ExpandMessageXmd: msg uint8[n, msg_size], out uint8[n, len_in_bytes], dst bytes on the host;
+    asynchronous on torch's current stream."""
+    _h2c_call_dev("c25519_ExpandMessageXmd_dev", out, None, msg, dst, out.shape[1])
+
+
+def ed25519_MapToCurve_dev(p, u):
+    """Device form of ed25519_MapToCurve: u, p uint8[n, 32]; asynchronous on torch's current stream."""
+    n, d = u.shape[0], u.device
+    args = (_check(p, 32, "p", n, device=d), _check(u, 32, "u"))
+    with _on(u) as st:
+        _lib.check(_lib.load().ed25519_MapToCurve_dev(*args, n, st), "ed25519_MapToCurve_dev")
+
+
+def ed25519_HashToCurve_dev(p, msg, dst):
+    """Device form of ed25519_HashToCurve: msg uint8[n, msg_size], p uint8[n, 32], dst bytes on the host; asynchronous on torch's
+    current stream."""
+    _h2c_call_dev("ed25519_HashToCurve_dev", p, 32, msg, dst)
+
+
+def ed25519_EncodeToCurve_dev(p, msg, dst):
+    """Device form of ed25519_EncodeToCurve: msg uint8[n, msg_size], p uint8[n, 32], dst bytes on the host."""
+    _h2c_call_dev("ed25519_EncodeToCurve_dev", p, 32, msg, dst)
+
+
+def ristretto255_HashToGroup_dev(p, msg, dst):
+    """Device form of ristretto255_HashToGroup: msg uint8[n, msg_size], p uint8[n, 32], dst bytes on the host."""
+    _h2c_call_dev("ristretto255_HashToGroup_dev", p, 32, msg, dst)
+
+
+def ed25519_HashToScalar_dev(s, msg, dst):
+    """Device form of ed25519_HashToScalar: msg uint8[n, msg_size], s uint8[n, 32], dst bytes on the host."""
+    _h2c_call_dev("ed25519_HashToScalar_dev", s, 32, msg, dst)
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

@@ -875,6 +875,57 @@ int ed25519_ScalarIsCanonical_batch(int* ok, const unsigned char* s, size_t n)
                      [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_ScalarIsCanonical_dev(d[1], d[0], c, st); });
 }
 
+// hashing to the groups (engine_h2c.hip; csrc/h2c25519.cuh): the messages are staged like a signing call's, the DST stays on the host
+typedef int (*h2c_dev_fn)(void*, const void*, size_t, const void*, size_t, size_t, void*);
+
+static int h2c_batch(unsigned char* out, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n,
+                     h2c_dev_fn call_dev)
+{
+    if (int rc = h2c_check_args(out, msg, msg_size, dst, dst_len, 64)) return rc;
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ msg, nullptr, msg_size }, Arr{ nullptr, out, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], msg_size, dst, dst_len, c, st); });
+}
+
+int c25519_ExpandMessageXmd_batch(unsigned char* out, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len,
+                                  size_t len_in_bytes, size_t n)
+{
+    if (int rc = h2c_check_args(out, msg, msg_size, dst, dst_len, len_in_bytes)) return rc;
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ msg, nullptr, msg_size }, Arr{ nullptr, out, len_in_bytes } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return c25519_ExpandMessageXmd_dev(d[1], d[0], msg_size, dst, dst_len, len_in_bytes, c, st);
+                     });
+}
+
+int ed25519_MapToCurve_batch(unsigned char* p, const unsigned char* u, size_t n)
+{
+    if (!p || !u) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ u, nullptr, 32 }, Arr{ nullptr, p, 32 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_MapToCurve_dev(d[1], d[0], c, st); });
+}
+
+int ed25519_HashToCurve_batch(unsigned char* p, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n)
+{
+    return h2c_batch(p, msg, msg_size, dst, dst_len, n, ed25519_HashToCurve_dev);
+}
+
+int ed25519_EncodeToCurve_batch(unsigned char* p, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n)
+{
+    return h2c_batch(p, msg, msg_size, dst, dst_len, n, ed25519_EncodeToCurve_dev);
+}
+
+int ristretto255_HashToGroup_batch(unsigned char* p, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n)
+{
+    return h2c_batch(p, msg, msg_size, dst, dst_len, n, ristretto255_HashToGroup_dev);
+}
+
+int ed25519_HashToScalar_batch(unsigned char* s, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n)
+{
+    return h2c_batch(s, msg, msg_size, dst, dst_len, n, ed25519_HashToScalar_dev);
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

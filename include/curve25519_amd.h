@@ -423,6 +423,64 @@ int ed25519_ScalarInvert_dev(void *recip, void *ok, const void *s, size_t n, voi
 int ed25519_ScalarIsCanonical_batch(int *ok, const unsigned char *s, size_t n);
 int ed25519_ScalarIsCanonical_dev(void *ok, const void *s, size_t n, void *stream);
 
+/* Hashing to the groups: messages to edwards25519 points, ristretto255 elements and scalars on the device (RFC 9380; RFC 9497) --
+ * libsodium >= 1.0.19's crypto_core_ed25519_from_string[_ro] and crypto_core_ristretto255_from_string[_ro], RFC 9497's HashToGroup
+ * and HashToScalar -- so that the front of an OPRF / PSI / VRF pipeline (identifiers, passwords, set elements in; group elements
+ * out) is no host loop of SHA-512 calls in front of ristretto255_FromHash_*.  INTEGRATION.md maps the names.
+ * All messages of a call are msg_size bytes: msg is n rows of msg_size bytes, as in ed25519_SignMessage_*; msg_size == 0 is allowed
+ * and msg may then be NULL.  dst, the domain separation tag, is dst_len bytes in HOST memory in both forms, 1 <= dst_len <= 255.
+ * Outputs are n x 32 bytes (ExpandMessageXmd: n x len_in_bytes).
+ *   c25519_ExpandMessageXmd_*: out[i] = expand_message_xmd(msg[i], dst, len_in_bytes) of RFC 9380 section 5.3.1 with H = SHA-512
+ *     (b_in_bytes = 64, s_in_bytes = 128), 1 <= len_in_bytes <= 16320 (ell <= 255).  dst_len of 0 or above 255 is an argument
+ *     error: the RFC's oversize-DST hashing is not implemented.  len_in_bytes out of range is an argument error.
+ *   ed25519_MapToCurve_*: p[i] = map_to_curve_elligator2_edwards25519(u) of RFC 9380 section 6.8.2 as the 32-byte Ed25519 encoding,
+ *     NO cofactor cleared.  u is the 32 bytes of u[i] read little-endian with bit 255 masked, taken mod p (the rule
+ *     ristretto255_FromHash_* has for its halves).  The one exceptional input is u = 0 mod p, for which the Montgomery point has
+ *     y = 0: it gives the identity, 01 00 ... 00.  No u gives x = -1: (J - 1) / 2 is not a square mod p.
+ *   ed25519_HashToCurve_*: edwards25519_XMD:SHA-512_ELL2_RO_ under the caller's DST.  hash_to_field(msg, 2) is 96 expander bytes,
+ *     each 48-byte half big-endian mod p; two maps, one addition, times 8, encode.  The result is in the prime-order subgroup.
+ *   ed25519_EncodeToCurve_*: edwards25519_XMD:SHA-512_ELL2_NU_: the same with one field element (48 bytes) and one map.
+ *   ristretto255_HashToGroup_*: hash_to_ristretto255 of RFC 9380 appendix B: 64 expander bytes into ristretto255_FromHash's map.
+ *     With dst = "HashToGroup-" || contextString it is RFC 9497's HashToGroup for ristretto255-SHA512.
+ *   ed25519_HashToScalar_*: RFC 9497 section 4.1's rule for ristretto255: the 64 expander bytes read little-endian as a 512-bit
+ *     integer, mod L; the output is canonical.  With dst = "HashToScalar-" || contextString it is RFC 9497's HashToScalar.
+ *   Inputs are never written.  Every row of every output is written; a refused call writes nothing.
+ *   n == 0 returns 0, with or without a device; a null pointer (msg too, unless msg_size == 0) is an argument error, "null pointer"
+ *   in c25519_amd_last_error().  Without a device every other call fails with an error code and text: there is no CPU result.
+ *   *_dev forms never synchronise and take 16-byte aligned device pointers (rows are msg_size and len_in_bytes apart, whatever
+ *   alignment that gives them); *_batch forms stage through the calling thread's pipeline like their neighbours.
+ *   c25519_amd_last_shape is not written.
+ *   Secrecy.  Messages are secret (OPRF inputs, passwords), and so are the expander's output and u.  No branch condition and no load
+ *     or store address derives from them: the block loops run on the lengths, every CMOV of the map, its sgn0 fix-up and its
+ *     exceptional case are masks.  Lengths and the DST are public.
+ * One lane per element at every n, ONE kernel per call, no scratch leased and no device memory allocated: everything that is the
+ * same for the whole call -- the lengths, the DST, SHA-512's padding -- travels in the kernel's arguments (csrc/h2c25519.cuh), so a
+ * *_dev call can be captured into a graph and does not touch the state other streams keep in flight.  b_0 starts from the constant
+ * state behind Z_pad's block of zeros; a message of msg_size bytes costs ceil((msg_size + dst_len + 21) / 128) compressions for
+ * b_0 and ceil((dst_len + 83) / 128) for each b_i.  The Edwards encoding's inversion is the lane's own (division steps).
+ * Measured (tools/h2c_rate.py, profiles/h2c_rate.txt; interleaved rounds, messages of 32 bytes, DSTs of 32 / 64 bytes -- a one- and a
+ * two-block b_i --, ristretto255_FromHash_dev of the same build on the same n beside each): at 2^20 HashToGroup_dev takes 2.60 / 2.69 ms
+ * (403 / 390 M/s) against 2.42 ms for FromHash_dev alone, 1.07 x / 1.11 x: the expander's two / three compressions, 0.20 / 0.28 ms as
+ * ExpandMessageXmd_dev of 64 bytes (5.3 / 3.7 G/s), are what it adds, as the operation counts said.  HashToCurve_dev 2.40 / 2.57 ms
+ * (438 / 408 M/s: two square-root chains, one inversion, three / five compressions), EncodeToCurve_dev 1.44 / 1.53 ms (729 / 686 M/s),
+ * MapToCurve_dev 1.19 ms (881 M/s), HashToScalar_dev 0.19 / 0.28 ms (5.4 / 3.7 G/s); ed25519_SignMessage_dev on the same messages:
+ * 1.17 ms.  Up to 2^16 elements a call is one lane's latency: 0.21 ms for HashToGroup, 0.18-0.20 for HashToCurve, 0.11-0.12 for
+ * EncodeToCurve, 0.10 for MapToCurve, 0.02-0.03 ms for HashToScalar and the expander. */
+int c25519_ExpandMessageXmd_batch(unsigned char *out /* n x len_in_bytes */, const unsigned char *msg, size_t msg_size,
+                                  const unsigned char *dst, size_t dst_len, size_t len_in_bytes, size_t n);
+int c25519_ExpandMessageXmd_dev(void *out, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len,
+                                size_t len_in_bytes, size_t n, void *stream);
+int ed25519_MapToCurve_batch(unsigned char *p, const unsigned char *u, size_t n);
+int ed25519_MapToCurve_dev(void *p, const void *u, size_t n, void *stream);
+int ed25519_HashToCurve_batch(unsigned char *p, const unsigned char *msg, size_t msg_size, const unsigned char *dst, size_t dst_len, size_t n);
+int ed25519_HashToCurve_dev(void *p, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len, size_t n, void *stream);
+int ed25519_EncodeToCurve_batch(unsigned char *p, const unsigned char *msg, size_t msg_size, const unsigned char *dst, size_t dst_len, size_t n);
+int ed25519_EncodeToCurve_dev(void *p, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len, size_t n, void *stream);
+int ristretto255_HashToGroup_batch(unsigned char *p, const unsigned char *msg, size_t msg_size, const unsigned char *dst, size_t dst_len, size_t n);
+int ristretto255_HashToGroup_dev(void *p, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len, size_t n, void *stream);
+int ed25519_HashToScalar_batch(unsigned char *s, const unsigned char *msg, size_t msg_size, const unsigned char *dst, size_t dst_len, size_t n);
+int ed25519_HashToScalar_dev(void *s, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len, size_t n, void *stream);
+
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
  * element through the reference's own operation order in a kernel behind the walk.  Measured at n = 2^20

@@ -712,6 +712,59 @@ def main():
                     carry32(add(P1[2], P1[2]))):
         reduced(v, "ristretto255 FromHash addition")
     print("ristretto255 square-root step, decode, encode (with T and re-formed), Elligator map: ok")
+    # ---- h2c25519.cuh: the 48-byte reduction and the Elligator 2 map to the Edwards curve (RFC 9380 appendix G.2) ----
+    def h2c_fe_from_be48():
+        hi = [M26, M25, M26, M25, M26] + [0] * 5              # 128 bits through fe_from_words: five limbs (bit 255 of `hi` is clear)
+        a = [FROM_WORDS[i] + 38 * hi[i] for i in range(10)]
+        need(all(x <= U32 for x in a), "be48: lo + 38 hi overflows 32 bits")
+        need(beta(a) <= CONTRACT["carry32"], f"be48: beta {beta(a):.2f} outside fe_carry32's contract")
+        return reduced(carry32(a, "be48 carry"), "be48")
+
+    def h2c_eq(a, b, what):                                  # fe_sub, then rist_is_zero's fe_to_words
+        to_words(sub(a, b, f"{what} sub"), f"{what} to_words")
+
+    def h2c_map(u):
+        J = [486662] + [0] * 9
+        tv1 = reduced(carry32(add(sqr(u, "h2c u^2"), sqr(u, "h2c u^2")), "h2c tv1"), "h2c tv1")
+        xd = add(tv1, ONE)
+        tv2 = sqr(xd, "h2c xd^2")
+        gxd = mul(tv2, xd, "h2c gxd")
+        gx1 = mul(mul(tv1, J, "h2c J tv1"), CANON, "h2c x1n J tv1")
+        gx1 = mul(add(gx1, tv2), CANON, "h2c gx1")
+        tv3 = sqr(gxd, "h2c gxd^2")
+        tv2 = sqr(tv3, "h2c gxd^4")
+        tv3 = mul(mul(tv3, gxd, "h2c gxd^3"), gx1, "h2c gx1 gxd^3")
+        tv2 = mul(tv2, tv3, "h2c gx1 gxd^7")
+        chain250(tv2, R)
+        y11 = mul(R, tv3, "h2c y11")
+        y12 = mul(y11, CANON, "h2c y12")
+        h2c_eq(mul(sqr(y11, "h2c y11^2"), gxd, "h2c y11^2 gxd"), gx1, "h2c e1")
+        y1 = select(y11, y12)
+        x2n = mul(tv1, CANON, "h2c x2n")
+        y21 = mul(mul(y11, u, "h2c y11 u"), CANON, "h2c y21")
+        y22 = mul(y21, CANON, "h2c y22")
+        gx2 = mul(gx1, tv1, "h2c gx2")
+        h2c_eq(mul(sqr(y21, "h2c y21^2"), gxd, "h2c y21^2 gxd"), gx2, "h2c e2")
+        y2 = select(y21, y22)
+        h2c_eq(mul(sqr(y1, "h2c y1^2"), gxd, "h2c y1^2 gxd"), gx1, "h2c e3")
+        xn, y = select(CANON, x2n), select(y1, y2)
+        y = rist_abs(y, "h2c sgn0 fix-up")                   # fe_to_words for the parity, then rist_cneg
+        en, ed = mul(xn, CANON, "h2c xn c1"), mul(xd, y, "h2c xd y")
+        yn = reduced(carry32(sub(xn, xd, "h2c xn - xd")), "h2c yn")
+        yd = reduced(carry32(add(xn, xd)), "h2c yd")
+        to_words(mul(ed, yd, "h2c denominators"), "h2c exceptional")
+        en, ed, yn, yd = select(en, [0] * 10), select(ed, ONE), select(yn, ONE), select(yd, ONE)
+        return (reduced(mul(en, yd, "h2c X"), "h2c X"), reduced(mul(yn, ed, "h2c Y"), "h2c Y"), reduced(mul(ed, yd, "h2c Z"), "h2c Z"),
+                reduced(mul(en, yn, "h2c T"), "h2c T"))
+
+    Q = h2c_map(select(h2c_fe_from_be48(), FROM_WORDS))      # u from 48 expander bytes, or MapToCurve's 32 with bit 255 masked
+    for v in ge_add(*Q, carry32(add(Q[1], Q[0])), carry32(sub(Q[1], Q[0], "h2c pe ymx")), mul(Q[3], CANON, "h2c pe t2d"),
+                    carry32(add(Q[2], Q[2]))):
+        reduced(v, "HashToCurve addition")
+    for v in ge_double(R, R, R):
+        reduced(v, "HashToCurve doubling")
+    to_words(mul(R, R, "h2c affine"), "h2c encode to_words")
+    print("hash to curve: 48-byte reduction (beta 39 into one carry pass), Elligator 2 map, addition, doublings, encoding: ok")
     quad_section(R)
     print("quad25519 ladder step, addition, doubling, batch-inversion exchange: ok")
     small = coop_section(R)

@@ -121,6 +121,67 @@ assert all(L_LIMBS30[i] for i in (0, 1, 2, 3, 4)) and L_LIMBS30[5:8] == [0, 0, 0
 assert L * L_INV30 % 2**30 == 1 and L_INV30 == 0x2DAB81E5
 
 
+# hashing to the curve (RFC 9380; h2c25519.cuh).  The Elligator 2 map to curve25519 (J = 486662, Z = 2) in appendix G.2.1's
+# straight-line form needs -J, c2 = 2^((p + 3) / 8) (which turns a root of gx1 times u into a root of gx2 = 2 u^2 gx1) and sqrt(-1);
+# the rational map to the Edwards curve (6.8.2) needs sqrt(-486664) with sgn0 = 0, the even root.
+MONT_J = 486662
+H2C_NEG_J = p - MONT_J
+H2C_C2 = pow(2, (p + 3) // 8, p)
+H2C_SQRT_M486664 = even(sqrt_mod(-(MONT_J + 2) % p))
+assert H2C_SQRT_M486664 == 0x0F26EDF460A006BBD27B08DC03FC4F7EC5A1D3D14B7D1A82CC6E04AAFF457E06
+assert H2C_SQRT_M486664 ** 2 % p == -(MONT_J + 2) % p and H2C_SQRT_M486664 % 2 == 0
+assert H2C_C2 ** 4 % p == p - 4 and pow(-MONT_J % p, (p - 1) // 2, p) == p - 1          # -J is no square: u = 0 maps to (0, 0)
+assert pow((MONT_J - 1) * inv(2) % p, (p - 1) // 2, p) == p - 1                          # (J - 1) / 2 neither: no u gives x = -1
+
+
+# SHA-512's constants from their definition (FIPS 180-4 section 4.2.3, 5.3.5: the fractional parts of the cube and square roots of
+# the first primes) and its compression function, to give the state after Z_pad, the 128 zero bytes every b_0 of expand_message_xmd
+# starts with (RFC 9380 section 5.3.1): a constant of the suite, so no lane compresses that block.
+def _iroot(n, k):
+    lo, hi = 0, 1 << (n.bit_length() // k + 1)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if mid ** k <= n else (lo, mid - 1)
+    return lo
+
+
+M64 = 2**64 - 1
+_primes = [q for q in range(2, 410) if all(q % r for r in range(2, q))][:80]
+SHA512_K = [_iroot(q << 192, 3) & M64 for q in _primes]
+SHA512_IV = [_iroot(q << 128, 2) & M64 for q in _primes[:8]]
+assert SHA512_K[0] == 0x428A2F98D728AE22 and SHA512_K[79] == 0x6C44198C4A475817 and SHA512_IV[0] == 0x6A09E667F3BCC908
+
+
+def sha512_compress(state, block):
+    rotr = lambda x, n: (x >> n | x << (64 - n)) & M64      # noqa: E731
+    w = [int.from_bytes(block[8 * i:8 * i + 8], "big") for i in range(16)]
+    for i in range(16, 80):
+        s0 = rotr(w[i - 15], 1) ^ rotr(w[i - 15], 8) ^ w[i - 15] >> 7
+        s1 = rotr(w[i - 2], 19) ^ rotr(w[i - 2], 61) ^ w[i - 2] >> 6
+        w.append((w[i - 16] + s0 + w[i - 7] + s1) & M64)
+    a, b, c, dd, e, f, g, h = state
+    for i in range(80):
+        t1 = (h + (rotr(e, 14) ^ rotr(e, 18) ^ rotr(e, 41)) + (e & f ^ ~e & g) + SHA512_K[i] + w[i]) & M64
+        t2 = ((rotr(a, 28) ^ rotr(a, 34) ^ rotr(a, 39)) + (a & b ^ a & c ^ b & c)) & M64
+        a, b, c, dd, e, f, g, h = (t1 + t2) & M64, a, b, c, (dd + t1) & M64, e, f, g
+    return [(x + y) & M64 for x, y in zip(state, (a, b, c, dd, e, f, g, h))]
+
+
+def _sha512_check():
+    import hashlib
+    msg = b"abc"
+    block = msg + b"\x80" + bytes(128 - 1 - 16 - len(msg)) + (8 * len(msg)).to_bytes(16, "big")
+    got = b"".join(x.to_bytes(8, "big") for x in sha512_compress(SHA512_IV, block))
+    assert got == hashlib.sha512(msg).digest()
+    mid = sha512_compress(SHA512_IV, bytes(128))
+    tail = b"\x80" + bytes(128 - 1 - 16) + (8 * 128).to_bytes(16, "big")
+    assert b"".join(x.to_bytes(8, "big") for x in sha512_compress(mid, tail)) == hashlib.sha512(bytes(128)).digest()
+    return mid
+
+
+SHA512_ZPAD_MID = _sha512_check()
+
+
 def words(v):
     return ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xFFFFFFFF) for i in range(8))
 
@@ -137,6 +198,9 @@ consts = [
     ("K_SQRT_AD_MINUS_ONE", SQRT_AD_MINUS_ONE, "ristretto255: sqrt(a d - 1), the odd root"),
     ("K_ONE_MINUS_D_SQ", ONE_MINUS_D_SQ, "ristretto255: 1 - d^2"),
     ("K_D_MINUS_ONE_SQ", D_MINUS_ONE_SQ, "ristretto255: (d - 1)^2"),
+    ("K_H2C_NEG_J", H2C_NEG_J, "hash to curve: -J = -486662, the first x of Elligator 2 on curve25519"),
+    ("K_H2C_C2", H2C_C2, "hash to curve: 2^((p + 3) / 8)"),
+    ("K_H2C_SQRT_M486664", H2C_SQRT_M486664, "hash to curve: sqrt(-486664), the even root"),
 ]
 out = ["// GENERATED by tools/gen_constants.py -- do not edit.  256-bit little-endian 32-bit words.",
        "#pragma once", "#include <stdint.h>", "namespace c25519 {"]
@@ -165,6 +229,8 @@ out.append("// one at bit 252, the others below bit %d), bit i of K_L_NAF_NEG wh
            % (L_NAF_NZ & ((1 << 252) - 1)).bit_length())
 out.append("__device__ constexpr uint32_t K_L_NAF_NZ[8] = { %s };" % words(L_NAF_NZ))
 out.append("__device__ constexpr uint32_t K_L_NAF_NEG[8] = { %s };" % words(L_NAF_NEG))
+out.append("// SHA-512's state after the 128 zero bytes of Z_pad (RFC 9380 section 5.3.1): where every b_0 starts")
+out.append("__device__ constexpr uint64_t K_SHA512_ZPAD_MID[8] = { %s };" % ", ".join("0x%016xull" % v for v in SHA512_ZPAD_MID))
 out.append("}  // namespace c25519")
 path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "curve25519_amd", "csrc", "curve_constants.cuh")
 open(path, "w").write("\n".join(out) + "\n")
