@@ -96,6 +96,12 @@ SIGNATURES = {
     "ristretto255_HashToGroup_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
     "ed25519_HashToScalar_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
     "ed25519_HashToScalar_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
+    "ed25519_VRF_Prove_batch": [_vp, _vp, _vp, _sz, _sz],
+    "ed25519_VRF_Prove_dev": [_vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VRF_Verify_batch": [_vp, _vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VRF_Verify_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ed25519_VRF_ProofToHash_batch": [_vp, _vp, _vp, _sz],
+    "ed25519_VRF_ProofToHash_dev": [_vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],

@@ -375,6 +375,51 @@ def ed25519_HashToScalar(msg, dst):
     return _h2c_call("ed25519_HashToScalar_batch", msg, dst)
 
 
+def _vrf_alpha(alpha, n):
+    """alpha uint8[n, alpha_size]: the rows of a VRF call's inputs (alpha_size may be 0)"""
+    alpha = np.ascontiguousarray(alpha, dtype=np.uint8)
+    if alpha.ndim != 2 or alpha.shape[0] != n:
+        raise ValueError(f"alpha must have shape ({n}, alpha_size), got {alpha.shape}")
+    return alpha
+
+
+def ed25519_VRF_Prove(priv, alpha):
+    """n x ECVRF-EDWARDS25519-SHA512-ELL2 prove (RFC 9381 section 5.1): priv uint8[n, 64] (seed || public key, the public half read
+    as given), alpha uint8[n, alpha_size] -> the proofs uint8[n, 80], Gamma || c || s."""
+    priv = _np(priv, 64, "priv")
+    n = priv.shape[0]
+    alpha = _vrf_alpha(alpha, n)
+    proof = np.empty((n, 80), np.uint8)
+    _lib.check(_lib.load().ed25519_VRF_Prove_batch(_ptr(proof), _ptr(priv), _ptr(alpha) if alpha.shape[1] else None, alpha.shape[1], n),
+               "ed25519_VRF_Prove_batch")
+    return proof
+
+
+def ed25519_VRF_Verify(pk, proof, alpha):
+    """n x ECVRF verify with validate_key = TRUE (RFC 9381 section 5.3): pk uint8[n, 32], proof uint8[n, 80], alpha
+    uint8[n, alpha_size].  Returns (beta uint8[n, 64], ok int32[n]): ok = 1 and the VRF output where the proof is valid, ok = 0 and
+    64 zero bytes where it is not."""
+    pk, proof = _np(pk, 32, "pk"), _np(proof, 80, "proof")
+    n = pk.shape[0]
+    if proof.shape[0] != n:
+        raise ValueError("pk and proof must have the same number of rows")
+    alpha = _vrf_alpha(alpha, n)
+    beta, ok = np.empty((n, 64), np.uint8), np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_VRF_Verify_batch(_ptr(beta), _ptr(ok), _ptr(pk), _ptr(proof), _ptr(alpha) if alpha.shape[1] else None,
+                                                    alpha.shape[1], n), "ed25519_VRF_Verify_batch")
+    return beta, ok
+
+
+def ed25519_VRF_ProofToHash(proof):
+    """n x ECVRF proof_to_hash (RFC 9381 section 5.2): proof uint8[n, 80].  Returns (beta uint8[n, 64], ok int32[n]): ok = 0 and 64
+    zero bytes where the proof does not decode.  The proof is NOT verified."""
+    proof = _np(proof, 80, "proof")
+    n = proof.shape[0]
+    beta, ok = np.empty((n, 64), np.uint8), np.empty(n, np.int32)
+    _lib.check(_lib.load().ed25519_VRF_ProofToHash_batch(_ptr(beta), _ptr(ok), _ptr(proof), n), "ed25519_VRF_ProofToHash_batch")
+    return beta, ok
+
+
 def ed25519_SignMessage(priv, msg):
     """n x ed25519_SignMessage(blinding=NULL) over fixed-length messages msg[n, msg_size]."""
     priv = _np(priv, 64, "priv")
@@ -1006,6 +1051,37 @@ def ristretto255_HashToGroup_dev(p, msg, dst):
 def ed25519_HashToScalar_dev(s, msg, dst):
     """Device form of ed25519_HashToScalar: msg uint8[n, msg_size], s uint8[n, 32], dst bytes on the host."""
     _h2c_call_dev("ed25519_HashToScalar_dev", s, 32, msg, dst)
+
+
+def ed25519_VRF_Prove_dev(proof, priv, alpha):
+    """Device form of ed25519_VRF_Prove: priv uint8[n, 64], alpha uint8[n, alpha_size], proof uint8[n, 80]; asynchronous on torch's
+    current stream."""
+    n, d = priv.shape[0], priv.device
+    args = (_check(proof, 80, "proof", n, device=d), _check(priv, 64, "priv"),
+            _check(alpha, None, "alpha", n, device=d) if alpha.shape[1] else None)
+    with _on(priv) as st:
+        _lib.check(_lib.load().ed25519_VRF_Prove_dev(*args, alpha.shape[1], n, st), "ed25519_VRF_Prove_dev")
+
+
+def ed25519_VRF_Verify_dev(beta, ok, pk, proof, alpha):
+    """Device form of ed25519_VRF_Verify: pk uint8[n, 32], proof uint8[n, 80], alpha uint8[n, alpha_size], beta uint8[n, 64],
+    ok int32[n, 1]; asynchronous on torch's current stream."""
+    import torch
+    n, d = pk.shape[0], pk.device
+    args = (_check(beta, 64, "beta", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(pk, 32, "pk"),
+            _check(proof, 80, "proof", n, device=d), _check(alpha, None, "alpha", n, device=d) if alpha.shape[1] else None)
+    with _on(pk) as st:
+        _lib.check(_lib.load().ed25519_VRF_Verify_dev(*args, alpha.shape[1], n, st), "ed25519_VRF_Verify_dev")
+
+
+def ed25519_VRF_ProofToHash_dev(beta, ok, proof):
+    """Device form of ed25519_VRF_ProofToHash: proof uint8[n, 80], beta uint8[n, 64], ok int32[n, 1]; asynchronous on torch's current
+    stream."""
+    import torch
+    n, d = proof.shape[0], proof.device
+    args = (_check(beta, 64, "beta", n, device=d), _check(ok, 1, "ok", n, dtype=torch.int32, device=d), _check(proof, 80, "proof"))
+    with _on(proof) as st:
+        _lib.check(_lib.load().ed25519_VRF_ProofToHash_dev(*args, n, st), "ed25519_VRF_ProofToHash_dev")
 
 
 def ed25519_SignMessage_dev(sig, priv, msg):

@@ -926,6 +926,35 @@ int ed25519_HashToScalar_batch(unsigned char* s, const unsigned char* msg, size_
     return h2c_batch(s, msg, msg_size, dst, dst_len, n, ed25519_HashToScalar_dev);
 }
 
+// ECVRF (engine_vrf.hip; csrc/vrf25519.cuh): alpha is staged like a signing call's messages
+int ed25519_VRF_Prove_batch(unsigned char* proof, const unsigned char* priv, const unsigned char* alpha, size_t alpha_size, size_t n)
+{
+    if (!proof || !priv || (!alpha && alpha_size)) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ alpha, nullptr, alpha_size }, Arr{ nullptr, proof, 80 } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_VRF_Prove_dev(d[2], d[0], d[1], alpha_size, c, st); });
+}
+
+int ed25519_VRF_Verify_batch(unsigned char* beta, int* ok, const unsigned char* pk, const unsigned char* proof, const unsigned char* alpha,
+                             size_t alpha_size, size_t n)
+{
+    if (!beta || !ok || !pk || !proof || (!alpha && alpha_size)) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ proof, nullptr, 80 }, Arr{ alpha, nullptr, alpha_size }, Arr{ nullptr, beta, 64 },
+                          Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
+                         return ed25519_VRF_Verify_dev(d[3], d[4], d[0], d[1], d[2], alpha_size, c, st);
+                     });
+}
+
+int ed25519_VRF_ProofToHash_batch(unsigned char* beta, int* ok, const unsigned char* proof, size_t n)
+{
+    if (!beta || !ok || !proof) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return run_batch(n, { Arr{ proof, nullptr, 80 }, Arr{ nullptr, beta, 64 }, Arr{ nullptr, ok, sizeof(int) } },
+                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_VRF_ProofToHash_dev(d[1], d[2], d[0], c, st); });
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

@@ -108,6 +108,35 @@ C25519_DEV void h2c_b0(u64 (&b0)[8], const uint8_t* msg, const H2cTail& t)
     for (int i = 0; i < 8; i++) b0[i] = st[i];
 }
 
+// b_0 of a message whose first 32 bytes sit in registers as four stream words (pre: a key's bytes through sha512_words_from_le32)
+// and whose other 8 (msg_words - 4) + msg_rem bytes are at `rest`, any alignment (not read where there are none): the tail is the
+// one h2c_make_tail lays out for the whole length.  ECVRF's encode_to_curve(PK_string || alpha_string), vrf25519.cuh.
+C25519_DEV void h2c_b0_pre4(u64 (&b0)[8], const u64 (&pre)[4], const uint8_t* rest, const H2cTail& t)
+{
+    u64 st[8], w[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = K_SHA512_ZPAD_MID[i];
+    const size_t body = 8 * (size_t)(t.msg_words - 4);
+    u64 last = 0;
+#pragma unroll
+    for (u32 j = 0; j < 8; j++) last = (last << 8) | (j < t.msg_rem ? rest[body + j] : 0u);
+#pragma unroll 1
+    for (u32 blk = 0; blk < t.blocks0; blk++) {
+#pragma unroll
+        for (u32 j = 0; j < 16; j++) {
+            const u32 g = 16 * blk + j;
+            u64 v;
+            if (j < 4 && blk == 0) v = pre[j];
+            else if (g < t.msg_words) v = sha512_msg_word(rest, body, g - 4);
+            else v = t.w0[g - t.msg_words] | (g == t.msg_words ? last : 0);
+            w[j] = v;
+        }
+        sha512_compress(st, w);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) b0[i] = st[i];
+}
+
 // b_i = H(in || i || DST'): in is b_0 for i = 1, b_0 xor b_(i-1) beyond
 C25519_DEV void h2c_bi(u64 (&out)[8], const u64 (&in)[8], u32 i, const H2cTail& t)
 {

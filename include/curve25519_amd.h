@@ -481,6 +481,59 @@ int ristretto255_HashToGroup_dev(void *p, const void *msg, size_t msg_size, cons
 int ed25519_HashToScalar_batch(unsigned char *s, const unsigned char *msg, size_t msg_size, const unsigned char *dst, size_t dst_len, size_t n);
 int ed25519_HashToScalar_dev(void *s, const void *msg, size_t msg_size, const void *dst /* host */, size_t dst_len, size_t n, void *stream);
 
+/* A verifiable random function: ECVRF-EDWARDS25519-SHA512-ELL2 of RFC 9381 (suite string 0x04), many proofs over many keys in one
+ * call -- what leader election and sortition, key transparency and NSEC5 prove once and verify in bulk.  One lane program per call
+ * does what ed25519_EncodeToCurve, two ed25519_ScalarMult_noclamp, ed25519_ScalarMultBase_noclamp, ed25519_ScalarMulAdd and three
+ * host hashes would: x, k and the hash prefix stay in registers from the seed to the proof, no intermediate point is encoded only
+ * to be decoded again, and the proof's fields are checked as the RFC requires.
+ * Constants of the suite: suite_string = 0x04; the hash_to_curve DST is "ECVRF_" || "edwards25519_XMD:SHA-512_ELL2_NU_" || 0x04
+ * (40 bytes); cLen = 16, qLen = ptLen = 32; the cofactor is 8.  All inputs of a call share one alpha_size, as the hashing calls'
+ * messages share msg_size: alpha is n rows of alpha_size bytes; alpha_size == 0 is allowed and alpha may then be NULL.
+ *   ed25519_VRF_Prove_* (sections 5.1, 5.4.1.2, 5.4.2.2, 5.4.3): priv[i] is the reference's 64-byte private key, seed || public key.
+ *     h = SHA-512(seed); x = h[0..31] clamped; Y_string = priv[i][32..63], read AS GIVEN as ed25519_SignMessage reads it: not
+ *     recomputed, not checked.  H = encode_to_curve(Y_string || alpha) under the DST above (ed25519_EncodeToCurve's rule);
+ *     Gamma = [x]H; k = SHA-512(h[32..63] || H_string) read little-endian mod L; U = [k]B, V = [k]H; c = the first 16 bytes of
+ *     SHA-512(0x04 || 0x02 || Y_string || H_string || Gamma_string || U_string || V_string || 0x00); s = k + c x mod L.
+ *     proof[i] = Gamma_string || c || s, 80 bytes, all three canonical encodings.
+ *   ed25519_VRF_ProofToHash_* (5.2, 5.4.4): ok[i] = 1 exactly when bytes 0..31 of proof[i] decode canonically -- RFC 8032's decoding:
+ *     ed25519_ClassifyKey's DECODES and CANONICAL -- and s < L; then beta[i] = SHA-512(0x04 || 0x03 || enc([8]Gamma) || 0x00).
+ *     Otherwise ok[i] = 0 and beta[i] is 64 zero bytes.
+ *   ed25519_VRF_Verify_* (5.3 with validate_key = TRUE, 5.4.5): ok[i] = 1 exactly when pk[i] decodes canonically, pk[i] is not of
+ *     small order, the proof decodes as above, and with H as above, U = [s]B - [c]Y and V = [s]H - [c]Gamma the 16 bytes recomputed
+ *     from (Y, H, Gamma, U, V) equal the proof's c.  Then beta[i] is as in ProofToHash; otherwise ok[i] = 0 and beta[i] is zeros.
+ *     There is no torsion-freeness rule: the RFC has none (a key of mixed order is accepted when the equations hold).
+ *   Inputs are never written.  Every row of every output is written; a refused call writes nothing.
+ *   n == 0 returns 0, with or without a device; a null pointer (alpha too, unless alpha_size == 0) is an argument error, "null pointer"
+ *   in c25519_amd_last_error().  Without a device every other call fails with an error code and text: there is no CPU result.
+ *   *_dev forms never synchronise and take 16-byte aligned device pointers (rows are 80, 64, 32 and alpha_size bytes apart, whatever
+ *   alignment that gives them); *_batch forms stage through the calling thread's pipeline like their neighbours.
+ *   c25519_amd_last_shape is not written.
+ *   Secrecy.  In Prove the seed, h, x, k and what s is computed from are secret; Y, alpha, H, Gamma, U, V and c are public.  No
+ *     branch condition and no load or store address derives from a secret, with the one exception of the base comb's row fetch for
+ *     [k]B, exactly as in signing; no secret is written to device memory (k's comb columns are parked in LDS, as a signing nonce's
+ *     are).  Everything in Verify and ProofToHash is public.
+ * One lane per element at every n, ONE kernel per call, no scratch leased and no device memory allocated (csrc/vrf25519.cuh,
+ * csrc/engine_vrf.hip): a *_dev call can be captured into a graph as one node.  [x]H and [k]H walk one table of H; the three
+ * encodings of a proof share one inversion, H_string and H's table another; Verify walks half-length digits for the 128 bits of c.
+ * Prove runs at two waves per SIMD (249 registers), Verify at one (415), ProofToHash at two (143); none has scratch.
+ * Measured (tools/vrf_rate.py, profiles/vrf_rate.txt; interleaved rounds, alpha of 32 bytes, beside each call on the same inputs in
+ * the same process the composed sequence a caller had before -- EncodeToCurve_dev, two ScalarMult_noclamp_dev,
+ * ScalarMultBase_noclamp_dev, ScalarMulAdd_dev, without its three host hashes -- and one ScalarMult_noclamp_dev): at 2^20 Prove_dev
+ * takes 23.22 ms (45.2 M proofs/s; spread of the rounds 0.04 ms) against 25.14 ms (spread 0.04) for the composed sequence, 0.92 x, and
+ * 11.41 ms for one ScalarMult_noclamp_dev, 2.03 x; Verify_dev 29.64 ms (35.4 M/s; spread 0.06), 1.18 x composed and 1.28 x Prove;
+ * ProofToHash_dev 1.28 ms (817 M/s).  Up to 2^16 elements a call is one lane's latency: 1.66-1.69 ms for Prove (composed:
+ * 1.87-1.92), 1.83-1.86 for Verify, 0.10 ms for ProofToHash. */
+#define ed25519_vrf_proof_size  80
+#define ed25519_vrf_output_size 64
+int ed25519_VRF_Prove_batch(unsigned char *proof /* n x 80 */, const unsigned char *priv /* n x 64 */,
+                            const unsigned char *alpha, size_t alpha_size, size_t n);
+int ed25519_VRF_Prove_dev(void *proof, const void *priv, const void *alpha, size_t alpha_size, size_t n, void *stream);
+int ed25519_VRF_Verify_batch(unsigned char *beta /* n x 64 */, int *ok, const unsigned char *pk, const unsigned char *proof,
+                             const unsigned char *alpha, size_t alpha_size, size_t n);
+int ed25519_VRF_Verify_dev(void *beta, void *ok, const void *pk, const void *proof, const void *alpha, size_t alpha_size, size_t n, void *stream);
+int ed25519_VRF_ProofToHash_batch(unsigned char *beta /* n x 64 */, int *ok, const unsigned char *proof, size_t n);
+int ed25519_VRF_ProofToHash_dev(void *beta, void *ok, const void *proof, size_t n, void *stream);
+
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
  * element through the reference's own operation order in a kernel behind the walk.  Measured at n = 2^20
