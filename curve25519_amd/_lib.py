@@ -8,112 +8,75 @@ from . import build as _build
 
 _vp, _sz = C.c_void_p, C.c_size_t
 
+# stem -> argtypes of <stem>_batch; <stem>_dev takes the same arguments and the stream behind them
+_PAIRS = {
+    "curve25519_dh_CreateSharedKey": [_vp, _vp, _vp, _sz],
+    "curve25519_dh_CreateSharedKey_one_peer": [_vp, _vp, _vp, _sz],
+    "curve25519_dh_Peer_Init": [_vp, _vp, _sz],
+    "curve25519_dh_CreateSharedKey_indexed": [_vp, _vp, _sz, _vp, _vp, _sz],
+    "curve25519_dh_CalculatePublicKey": [_vp, _vp, _sz],
+    "curve25519_dh_CalculatePublicKey_fast": [_vp, _vp, _sz],
+    "ed25519_CreateKeyPair": [_vp, _vp, _vp, _sz],
+    "ed25519_SignMessage": [_vp, _vp, _vp, _sz, _sz],
+    "ed25519_SignMessage_ragged": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_Sign_Init": [_vp, _vp, _sz],
+    "ed25519_SignMessage_indexed": [_vp, _vp, _sz, _vp, _vp, _sz, _sz],
+    "ed25519_SignMessage_indexed_ragged": [_vp, _vp, _sz, _vp, _vp, _vp, _sz],
+    "ed25519_ClassifyKey": [_vp, _vp, _sz],
+    "ed25519_PublicKey_to_X25519": [_vp, _vp, _vp, _sz],
+    "ed25519_PrivateKey_to_X25519": [_vp, _vp, _sz],
+    "ed25519_ScalarMult": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarMult_noclamp": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarMultBase": [_vp, _vp, _sz],
+    "ed25519_ScalarMultBase_noclamp": [_vp, _vp, _sz],
+    "ed25519_PointAdd": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_PointSub": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_IsValidPoint": [_vp, _vp, _sz],
+    "ristretto255_FromHash": [_vp, _vp, _sz],
+    "ristretto255_ScalarMult": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_ScalarMultBase": [_vp, _vp, _sz],
+    "ristretto255_PointAdd": [_vp, _vp, _vp, _vp, _sz],
+    "ristretto255_PointSub": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarReduce": [_vp, _vp, _sz],
+    "ed25519_ScalarAdd": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarSub": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarMul": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarNegate": [_vp, _vp, _sz],
+    "ed25519_ScalarComplement": [_vp, _vp, _sz],
+    "ed25519_ScalarMulAdd": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_ScalarInvert": [_vp, _vp, _vp, _sz],
+    "ed25519_ScalarIsCanonical": [_vp, _vp, _sz],
+    "c25519_ExpandMessageXmd": [_vp, _vp, _sz, _vp, _sz, _sz, _sz],
+    "ed25519_MapToCurve": [_vp, _vp, _sz],
+    "ed25519_HashToCurve": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_EncodeToCurve": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ristretto255_HashToGroup": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_HashToScalar": [_vp, _vp, _sz, _vp, _sz, _sz],
+    "ed25519_VRF_Prove": [_vp, _vp, _vp, _sz, _sz],
+    "ed25519_VRF_Verify": [_vp, _vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VRF_ProofToHash": [_vp, _vp, _vp, _sz],
+    "ed25519_VerifySignature_ragged": [_vp, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_VerifySignature": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VerifySignature_strict": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VerifySignature_strict_ragged": [_vp, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_VerifySignature_zip215": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_VerifySignature_zip215_ragged": [_vp, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_Verify_Init": [_vp, _vp, _sz],
+    "ed25519_Verify_Check": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_strict": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_indexed": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_indexed_ragged": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_Verify_Check_zip215": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_zip215_indexed": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_Verify_Check_zip215_indexed_ragged": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
+    "ed25519_CreateKeyPair_blinded": [_vp, _vp, _vp, _vp, _sz],
+    "ed25519_SignMessage_blinded": [_vp, _vp, _vp, _vp, _sz, _sz],
+}
+
 # name -> argtypes ; every function returns int (0 = ok) unless listed in _RESTYPE
 SIGNATURES = {
-    "curve25519_dh_CreateSharedKey_batch": [_vp, _vp, _vp, _sz],
-    "curve25519_dh_CreateSharedKey_dev": [_vp, _vp, _vp, _sz, _vp],
-    "curve25519_dh_CreateSharedKey_one_peer_batch": [_vp, _vp, _vp, _sz],
-    "curve25519_dh_CreateSharedKey_one_peer_dev": [_vp, _vp, _vp, _sz, _vp],
     "c25519_amd_x25519_one_peer_last_wide": [],
-    "curve25519_dh_Peer_Init_batch": [_vp, _vp, _sz],
-    "curve25519_dh_Peer_Init_dev": [_vp, _vp, _sz, _vp],
-    "curve25519_dh_CreateSharedKey_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _sz],
-    "curve25519_dh_CreateSharedKey_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _vp],
     "c25519_amd_x25519_indexed_last_ladder_elements": [],
-    "curve25519_dh_CalculatePublicKey_batch": [_vp, _vp, _sz],
-    "curve25519_dh_CalculatePublicKey_dev": [_vp, _vp, _sz, _vp],
-    "curve25519_dh_CalculatePublicKey_fast_batch": [_vp, _vp, _sz],
-    "curve25519_dh_CalculatePublicKey_fast_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_CreateKeyPair_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_CreateKeyPair_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_SignMessage_batch": [_vp, _vp, _vp, _sz, _sz],
-    "ed25519_SignMessage_dev": [_vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_SignMessage_ragged_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_SignMessage_ragged_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_Sign_Init_batch": [_vp, _vp, _sz],
-    "ed25519_Sign_Init_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_SignMessage_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _sz, _sz],
-    "ed25519_SignMessage_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_SignMessage_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz],
-    "ed25519_SignMessage_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_ClassifyKey_batch": [_vp, _vp, _sz],
-    "ed25519_ClassifyKey_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_PublicKey_to_X25519_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_PublicKey_to_X25519_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_PrivateKey_to_X25519_batch": [_vp, _vp, _sz],
-    "ed25519_PrivateKey_to_X25519_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_ScalarMult_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_ScalarMult_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarMult_noclamp_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_ScalarMult_noclamp_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarMultBase_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarMultBase_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_ScalarMultBase_noclamp_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarMultBase_noclamp_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_PointAdd_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ristretto255_IsValidPoint_batch": [_vp, _vp, _sz],
-    "ristretto255_IsValidPoint_dev": [_vp, _vp, _sz, _vp],
-    "ristretto255_FromHash_batch": [_vp, _vp, _sz],
-    "ristretto255_FromHash_dev": [_vp, _vp, _sz, _vp],
-    "ristretto255_ScalarMult_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ristretto255_ScalarMult_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ristretto255_ScalarMultBase_batch": [_vp, _vp, _sz],
-    "ristretto255_ScalarMultBase_dev": [_vp, _vp, _sz, _vp],
-    "ristretto255_PointAdd_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ristretto255_PointAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ristretto255_PointSub_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ristretto255_PointSub_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarReduce_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarReduce_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_ScalarAdd_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_ScalarAdd_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarSub_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_ScalarSub_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarMul_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_ScalarMul_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarNegate_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarNegate_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_ScalarComplement_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarComplement_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_ScalarMulAdd_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_ScalarMulAdd_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarInvert_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_ScalarInvert_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_ScalarIsCanonical_batch": [_vp, _vp, _sz],
-    "ed25519_ScalarIsCanonical_dev": [_vp, _vp, _sz, _vp],
-    "c25519_ExpandMessageXmd_batch": [_vp, _vp, _sz, _vp, _sz, _sz, _sz],
-    "c25519_ExpandMessageXmd_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp],
-    "ed25519_MapToCurve_batch": [_vp, _vp, _sz],
-    "ed25519_MapToCurve_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_HashToCurve_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
-    "ed25519_HashToCurve_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
-    "ed25519_EncodeToCurve_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
-    "ed25519_EncodeToCurve_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
-    "ristretto255_HashToGroup_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
-    "ristretto255_HashToGroup_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
-    "ed25519_HashToScalar_batch": [_vp, _vp, _sz, _vp, _sz, _sz],
-    "ed25519_HashToScalar_dev": [_vp, _vp, _sz, _vp, _sz, _sz, _vp],
-    "ed25519_VRF_Prove_batch": [_vp, _vp, _vp, _sz, _sz],
-    "ed25519_VRF_Prove_dev": [_vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_VRF_Verify_batch": [_vp, _vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_VRF_Verify_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_VRF_ProofToHash_batch": [_vp, _vp, _vp, _sz],
-    "ed25519_VRF_ProofToHash_dev": [_vp, _vp, _vp, _sz, _vp],
-    "ed25519_VerifySignature_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
-    "ed25519_VerifySignature_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_VerifySignature_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_VerifySignature_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_VerifySignature_strict_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_VerifySignature_strict_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_VerifySignature_strict_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
-    "ed25519_VerifySignature_strict_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_VerifySignature_zip215_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_VerifySignature_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_VerifySignature_zip215_ragged_batch": [_vp, _vp, _vp, _vp, _vp, _sz],
-    "ed25519_VerifySignature_zip215_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_VerifyBatch_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "ed25519_VerifyBatch_zip215_ragged_dev": [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp],
     "ed25519_VerifyBatch_zip215_batch": [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp],
@@ -133,27 +96,7 @@ SIGNATURES = {
     "c25519_amd_last_shape": [],
     "c25519_amd_host_register": [_vp, _sz],
     "c25519_amd_host_unregister": [_vp],
-    "ed25519_Verify_Init_batch": [_vp, _vp, _sz],
-    "ed25519_Verify_Init_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_Verify_Check_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_Verify_Check_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_Verify_Check_strict_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_Verify_Check_strict_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_Verify_Check_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_Verify_Check_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_Verify_Check_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
-    "ed25519_Verify_Check_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_Verify_Check_zip215_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_Verify_Check_zip215_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_Verify_Check_zip215_indexed_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_Verify_Check_zip215_indexed_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
-    "ed25519_Verify_Check_zip215_indexed_ragged_batch": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz],
-    "ed25519_Verify_Check_zip215_indexed_ragged_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp],
     "ed25519_Blinding_Init_dev": [_vp, _vp, _sz, _vp],
-    "ed25519_CreateKeyPair_blinded_batch": [_vp, _vp, _vp, _vp, _sz],
-    "ed25519_CreateKeyPair_blinded_dev": [_vp, _vp, _vp, _vp, _sz, _vp],
-    "ed25519_SignMessage_blinded_batch": [_vp, _vp, _vp, _vp, _sz, _sz],
-    "ed25519_SignMessage_blinded_dev": [_vp, _vp, _vp, _vp, _sz, _sz, _vp],
     "c25519_amd_multi_create": [_vp, _vp, C.c_int],
     "c25519_amd_multi_destroy": [_vp],
     "c25519_amd_multi_device_count": [_vp],
@@ -192,6 +135,8 @@ SIGNATURES = {
     "ed25519_Verify_Check": [_vp, _vp, _vp, _sz],
     "ed25519_Verify_Finish": [_vp],
 }
+for _stem, _args in _PAIRS.items():
+    SIGNATURES[_stem + "_batch"], SIGNATURES[_stem + "_dev"] = _args, _args + [_vp]
 _RESTYPE = {
     "ed25519_VerifySignature_scratch_bytes": _sz,
     "ed25519_VerifyBatch_scratch_bytes": _sz,

@@ -3,6 +3,11 @@
 // (one of the engine's translation units: engine_common.cuh says which is which)
 #include "engine_common.cuh"
 
+using c25519_host::row_call;
+using c25519_host::In;
+using c25519_host::Out;
+using c25519_host::InOut;
+
 // ------------------------------------------------------------------------------------------------
 // unit-test hooks (the counterpart of the reference's ECP_SELF_TEST unit checks,
 // test/curve25519_selftest.c:624-741): one lane per input record, operations defined in lanes.cuh
@@ -295,16 +300,12 @@ int c25519_amd_base_table(unsigned char* out)
     return 0;
 }
 
-// ---- host-pointer entry points: stage, run the *_dev form, copy back (run_batch above) ---------------
+// ---- host-pointer entry points: stage, run the *_dev form, copy back (host_pipeline.hpp: row_call states a call's arrays in the
+// order of its *_dev prototype; the wrappers with work of their own before the pipeline hand run_batch their lists themselves) ----
 
 int curve25519_dh_CreateSharedKey_batch(unsigned char* shared, const unsigned char* pk, unsigned char* sk, size_t n)
 {
-    if (!shared || !pk || !sk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ sk, sk, 32 }, Arr{ nullptr, shared, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return curve25519_dh_CreateSharedKey_dev(d[2], d[0], d[1], c, st);
-                     });
+    return row_call(n, { Out(shared, 32), In(pk, 32), InOut(sk, 32) }, curve25519_dh_CreateSharedKey_dev);
 }
 
 // the peer key has a device buffer of its own per calling thread, uploaded once per call -- and only when its bytes differ from
@@ -326,12 +327,7 @@ int curve25519_dh_CreateSharedKey_one_peer_batch(unsigned char* shared, const un
 
 int curve25519_dh_Peer_Init_batch(void* ctx, const unsigned char* pk, size_t n)
 {
-    if (!ctx || !pk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, ctx, 1600 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return curve25519_dh_Peer_Init_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(ctx, 1600), In(pk, 32) }, curve25519_dh_Peer_Init_dev);
 }
 
 // many contexts in one call: every index is checked here (one >= n_ctx refuses the call before any work), the contexts are
@@ -362,19 +358,15 @@ int curve25519_dh_CreateSharedKey_indexed_batch(unsigned char* shared, const voi
                      });
 }
 
-static int public_batch(unsigned char* pk, unsigned char* sk, size_t n, bool fast)
+int curve25519_dh_CalculatePublicKey_batch(unsigned char* pk, unsigned char* sk, size_t n)
 {
-    if (!pk || !sk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ sk, sk, 32 }, Arr{ nullptr, pk, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return fast ? curve25519_dh_CalculatePublicKey_fast_dev(d[1], d[0], c, st)
-                                     : curve25519_dh_CalculatePublicKey_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(pk, 32), InOut(sk, 32) }, curve25519_dh_CalculatePublicKey_dev);
 }
 
-int curve25519_dh_CalculatePublicKey_batch(unsigned char* pk, unsigned char* sk, size_t n) { return public_batch(pk, sk, n, false); }
-int curve25519_dh_CalculatePublicKey_fast_batch(unsigned char* pk, unsigned char* sk, size_t n) { return public_batch(pk, sk, n, true); }
+int curve25519_dh_CalculatePublicKey_fast_batch(unsigned char* pk, unsigned char* sk, size_t n)
+{
+    return row_call(n, { Out(pk, 32), InOut(sk, 32) }, curve25519_dh_CalculatePublicKey_fast_dev);
+}
 
 // the blinding context of a host-pointer call: 192 bytes uploaded once per call into the thread's scratch lane
 static int upload_blinding(void** dctx, const void* blinding)
@@ -429,7 +421,7 @@ static int sign_batch(unsigned char* sig, const unsigned char* priv, const void*
 int ed25519_SignMessage_batch(unsigned char* sig, const unsigned char* priv, const unsigned char* msg,
                               size_t msg_size, size_t n)
 {
-    return sign_batch(sig, priv, nullptr, msg, msg_size, n);
+    return row_call(n, { Out(sig, 64), In(priv, 64), In(msg, msg_size) }, ed25519_SignMessage_dev, msg_size);
 }
 
 int ed25519_SignMessage_blinded_batch(unsigned char* sig, const unsigned char* priv, const void* blinding,
@@ -439,34 +431,22 @@ int ed25519_SignMessage_blinded_batch(unsigned char* sig, const unsigned char* p
     return sign_batch(sig, priv, blinding, msg, msg_size, n);
 }
 
-static int verify_batch(int* verdict, const unsigned char* sig, const unsigned char* pk, const unsigned char* msg, size_t msg_size,
-                        size_t n, VerifyRules rules)
-{
-    if (!verdict || !sig || !pk || (!msg && msg_size)) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ sig, nullptr, 64 }, Arr{ pk, nullptr, 32 }, Arr{ msg, nullptr, msg_size },
-                          Arr{ nullptr, verdict, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return verify_dev(d[3], d[0], d[1], fixed_msgs(d[2], msg_size), c, st, rules);
-                     });
-}
-
 int ed25519_VerifySignature_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                   const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_PLAIN);
+    return row_call(n, { Out(verdict, sizeof(int)), In(sig, 64), In(pk, 32), In(msg, msg_size) }, ed25519_VerifySignature_dev, msg_size);
 }
 
 int ed25519_VerifySignature_strict_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_STRICT);
+    return row_call(n, { Out(verdict, sizeof(int)), In(sig, 64), In(pk, 32), In(msg, msg_size) }, ed25519_VerifySignature_strict_dev, msg_size);
 }
 
 int ed25519_VerifySignature_zip215_batch(int* verdict, const unsigned char* sig, const unsigned char* pk,
                                          const unsigned char* msg, size_t msg_size, size_t n)
 {
-    return verify_batch(verdict, sig, pk, msg, msg_size, n, RULES_ZIP215);
+    return row_call(n, { Out(verdict, sizeof(int)), In(sig, 64), In(pk, 32), In(msg, msg_size) }, ed25519_VerifySignature_zip215_dev, msg_size);
 }
 
 // ragged messages (host_pipeline.hpp: run_ragged)
@@ -576,12 +556,7 @@ void ed25519_Blinding_Finish(void* context)
 // malloc'ed here, exactly as in the reference (ed25519_verify.c:179-237).
 int ed25519_Verify_Init_batch(void* ctx, const unsigned char* pk, size_t n)
 {
-    if (!ctx || !pk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, ctx, 2080 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_Verify_Init_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(ctx, 2080), In(pk, 32) }, ed25519_Verify_Init_dev);
 }
 
 static int verify_check_batch(int* verdict, const void* ctx, const unsigned char* sig, const unsigned char* msg, size_t msg_size,
@@ -678,201 +653,131 @@ int ed25519_Verify_Check_zip215_indexed_ragged_batch(int* verdict, const void* c
 
 int ed25519_Sign_Init_batch(void* ctx, const unsigned char* priv, size_t n)
 {
-    if (!ctx || !priv) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ nullptr, ctx, 128 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_Sign_Init_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(ctx, 128), In(priv, 64) }, ed25519_Sign_Init_dev);
 }
 
 // key classification and conversion to X25519 keys (engine_keys.hip; csrc/ed_keys.cuh)
 int ed25519_ClassifyKey_batch(uint32_t* flags, const unsigned char* pk, size_t n)
 {
-    if (!flags || !pk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, flags, sizeof(uint32_t) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_ClassifyKey_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(flags, sizeof(uint32_t)), In(pk, 32) }, ed25519_ClassifyKey_dev);
 }
 
 int ed25519_PublicKey_to_X25519_batch(unsigned char* xpk, int* ok, const unsigned char* pk, size_t n)
 {
-    if (!xpk || !ok || !pk) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ nullptr, xpk, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_PublicKey_to_X25519_dev(d[1], d[2], d[0], c, st);
-                     });
+    return row_call(n, { Out(xpk, 32), Out(ok, sizeof(int)), In(pk, 32) }, ed25519_PublicKey_to_X25519_dev);
 }
 
 int ed25519_PrivateKey_to_X25519_batch(unsigned char* xsk, const unsigned char* priv, size_t n)
 {
-    if (!xsk || !priv) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ nullptr, xsk, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_PrivateKey_to_X25519_dev(d[1], d[0], c, st);
-                     });
+    return row_call(n, { Out(xsk, 32), In(priv, 64) }, ed25519_PrivateKey_to_X25519_dev);
 }
 
 // the group operations (engine_group.hip; csrc/ed_group.cuh)
-static int scalarmult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n, bool clamp)
-{
-    if (!q || !ok || !scalar || !point) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    const auto call_dev = clamp ? ed25519_ScalarMult_dev : ed25519_ScalarMult_noclamp_dev;
-    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ point, nullptr, 32 }, Arr{ nullptr, q, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
-}
-
 int ed25519_ScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
 {
-    return scalarmult_batch(q, ok, scalar, point, n, true);
+    return row_call(n, { Out(q, 32), Out(ok, sizeof(int)), In(scalar, 32), In(point, 32) }, ed25519_ScalarMult_dev);
 }
 
 int ed25519_ScalarMult_noclamp_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
 {
-    return scalarmult_batch(q, ok, scalar, point, n, false);
+    return row_call(n, { Out(q, 32), Out(ok, sizeof(int)), In(scalar, 32), In(point, 32) }, ed25519_ScalarMult_noclamp_dev);
 }
 
-static int scalarmult_base_batch(unsigned char* q, const unsigned char* scalar, size_t n, bool clamp)
+int ed25519_ScalarMultBase_batch(unsigned char* q, const unsigned char* scalar, size_t n)
 {
-    if (!q || !scalar) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    const auto call_dev = clamp ? ed25519_ScalarMultBase_dev : ed25519_ScalarMultBase_noclamp_dev;
-    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ nullptr, q, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(q, 32), In(scalar, 32) }, ed25519_ScalarMultBase_dev);
 }
-
-int ed25519_ScalarMultBase_batch(unsigned char* q, const unsigned char* scalar, size_t n) { return scalarmult_base_batch(q, scalar, n, true); }
 
 int ed25519_ScalarMultBase_noclamp_batch(unsigned char* q, const unsigned char* scalar, size_t n)
 {
-    return scalarmult_base_batch(q, scalar, n, false);
-}
-
-static int point_add_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n, bool sub)
-{
-    if (!r || !ok || !p || !q) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    const auto call_dev = sub ? ed25519_PointSub_dev : ed25519_PointAdd_dev;
-    return run_batch(n, { Arr{ p, nullptr, 32 }, Arr{ q, nullptr, 32 }, Arr{ nullptr, r, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
+    return row_call(n, { Out(q, 32), In(scalar, 32) }, ed25519_ScalarMultBase_noclamp_dev);
 }
 
 int ed25519_PointAdd_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
 {
-    return point_add_batch(r, ok, p, q, n, false);
+    return row_call(n, { Out(r, 32), Out(ok, sizeof(int)), In(p, 32), In(q, 32) }, ed25519_PointAdd_dev);
 }
 
 int ed25519_PointSub_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
 {
-    return point_add_batch(r, ok, p, q, n, true);
+    return row_call(n, { Out(r, 32), Out(ok, sizeof(int)), In(p, 32), In(q, 32) }, ed25519_PointSub_dev);
 }
 
 // ristretto255 (engine_ristretto.hip; csrc/ristretto255.cuh)
 int ristretto255_IsValidPoint_batch(int* ok, const unsigned char* point, size_t n)
 {
-    if (!ok || !point) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ point, nullptr, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_IsValidPoint_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(ok, sizeof(int)), In(point, 32) }, ristretto255_IsValidPoint_dev);
 }
 
 int ristretto255_FromHash_batch(unsigned char* p, const unsigned char* hash, size_t n)
 {
-    if (!p || !hash) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ hash, nullptr, 64 }, Arr{ nullptr, p, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_FromHash_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(p, 32), In(hash, 64) }, ristretto255_FromHash_dev);
 }
 
 int ristretto255_ScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t n)
 {
-    if (!q || !ok || !scalar || !point) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ point, nullptr, 32 }, Arr{ nullptr, q, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_ScalarMult_dev(d[2], d[3], d[0], d[1], c, st); });
+    return row_call(n, { Out(q, 32), Out(ok, sizeof(int)), In(scalar, 32), In(point, 32) }, ristretto255_ScalarMult_dev);
 }
 
 int ristretto255_ScalarMultBase_batch(unsigned char* q, const unsigned char* scalar, size_t n)
 {
-    if (!q || !scalar) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ scalar, nullptr, 32 }, Arr{ nullptr, q, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ristretto255_ScalarMultBase_dev(d[1], d[0], c, st); });
-}
-
-static int rist_point_add_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n, bool sub)
-{
-    if (!r || !ok || !p || !q) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    const auto call_dev = sub ? ristretto255_PointSub_dev : ristretto255_PointAdd_dev;
-    return run_batch(n, { Arr{ p, nullptr, 32 }, Arr{ q, nullptr, 32 }, Arr{ nullptr, r, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[3], d[0], d[1], c, st); });
+    return row_call(n, { Out(q, 32), In(scalar, 32) }, ristretto255_ScalarMultBase_dev);
 }
 
 int ristretto255_PointAdd_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
 {
-    return rist_point_add_batch(r, ok, p, q, n, false);
+    return row_call(n, { Out(r, 32), Out(ok, sizeof(int)), In(p, 32), In(q, 32) }, ristretto255_PointAdd_dev);
 }
 
 int ristretto255_PointSub_batch(unsigned char* r, int* ok, const unsigned char* p, const unsigned char* q, size_t n)
 {
-    return rist_point_add_batch(r, ok, p, q, n, true);
+    return row_call(n, { Out(r, 32), Out(ok, sizeof(int)), In(p, 32), In(q, 32) }, ristretto255_PointSub_dev);
 }
 
 // the scalar field mod L (engine_scalar.hip; csrc/sc_invert.cuh)
-typedef int (*sc_unary_dev_fn)(void*, const void*, size_t, void*);
-typedef int (*sc_binary_dev_fn)(void*, const void*, const void*, size_t, void*);
-
-static int sc_unary_batch(unsigned char* r, const unsigned char* s, size_t in_bytes, size_t n, sc_unary_dev_fn call_dev)
+int ed25519_ScalarReduce_batch(unsigned char* r, const unsigned char* s, size_t n)
 {
-    if (!r || !s) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ s, nullptr, in_bytes }, Arr{ nullptr, r, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(r, 32), In(s, 64) }, ed25519_ScalarReduce_dev);
 }
 
-static int sc_binary_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n, sc_binary_dev_fn call_dev)
+int ed25519_ScalarNegate_batch(unsigned char* r, const unsigned char* s, size_t n)
 {
-    if (!z || !x || !y) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ x, nullptr, 32 }, Arr{ y, nullptr, 32 }, Arr{ nullptr, z, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[2], d[0], d[1], c, st); });
+    return row_call(n, { Out(r, 32), In(s, 32) }, ed25519_ScalarNegate_dev);
 }
 
-int ed25519_ScalarReduce_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 64, n, ed25519_ScalarReduce_dev); }
-int ed25519_ScalarNegate_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 32, n, ed25519_ScalarNegate_dev); }
-int ed25519_ScalarComplement_batch(unsigned char* r, const unsigned char* s, size_t n) { return sc_unary_batch(r, s, 32, n, ed25519_ScalarComplement_dev); }
-int ed25519_ScalarAdd_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarAdd_dev); }
-int ed25519_ScalarSub_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarSub_dev); }
-int ed25519_ScalarMul_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n) { return sc_binary_batch(z, x, y, n, ed25519_ScalarMul_dev); }
+int ed25519_ScalarComplement_batch(unsigned char* r, const unsigned char* s, size_t n)
+{
+    return row_call(n, { Out(r, 32), In(s, 32) }, ed25519_ScalarComplement_dev);
+}
+
+int ed25519_ScalarAdd_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n)
+{
+    return row_call(n, { Out(z, 32), In(x, 32), In(y, 32) }, ed25519_ScalarAdd_dev);
+}
+
+int ed25519_ScalarSub_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n)
+{
+    return row_call(n, { Out(z, 32), In(x, 32), In(y, 32) }, ed25519_ScalarSub_dev);
+}
+
+int ed25519_ScalarMul_batch(unsigned char* z, const unsigned char* x, const unsigned char* y, size_t n)
+{
+    return row_call(n, { Out(z, 32), In(x, 32), In(y, 32) }, ed25519_ScalarMul_dev);
+}
 
 int ed25519_ScalarMulAdd_batch(unsigned char* r, const unsigned char* a, const unsigned char* b, const unsigned char* c, size_t n)
 {
-    if (!r || !a || !b || !c) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ a, nullptr, 32 }, Arr{ b, nullptr, 32 }, Arr{ c, nullptr, 32 }, Arr{ nullptr, r, 32 } },
-                     [&](void** d, size_t cnt, size_t, hipStream_t st) -> int { return ed25519_ScalarMulAdd_dev(d[3], d[0], d[1], d[2], cnt, st); });
+    return row_call(n, { Out(r, 32), In(a, 32), In(b, 32), In(c, 32) }, ed25519_ScalarMulAdd_dev);
 }
 
 int ed25519_ScalarInvert_batch(unsigned char* recip, int* ok, const unsigned char* s, size_t n)
 {
-    if (!recip || !ok || !s) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ s, nullptr, 32 }, Arr{ nullptr, recip, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_ScalarInvert_dev(d[1], d[2], d[0], c, st); });
+    return row_call(n, { Out(recip, 32), Out(ok, sizeof(int)), In(s, 32) }, ed25519_ScalarInvert_dev);
 }
 
 int ed25519_ScalarIsCanonical_batch(int* ok, const unsigned char* s, size_t n)
 {
-    if (!ok || !s) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ s, nullptr, 32 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_ScalarIsCanonical_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(ok, sizeof(int)), In(s, 32) }, ed25519_ScalarIsCanonical_dev);
 }
 
 // hashing to the groups (engine_h2c.hip; csrc/h2c25519.cuh): the messages are staged like a signing call's, the DST stays on the host
@@ -882,28 +787,19 @@ static int h2c_batch(unsigned char* out, const unsigned char* msg, size_t msg_si
                      h2c_dev_fn call_dev)
 {
     if (int rc = h2c_check_args(out, msg, msg_size, dst, dst_len, 64)) return rc;
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ msg, nullptr, msg_size }, Arr{ nullptr, out, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return call_dev(d[1], d[0], msg_size, dst, dst_len, c, st); });
+    return row_call(n, { Out(out, 32), In(msg, msg_size) }, call_dev, msg_size, dst, dst_len);
 }
 
 int c25519_ExpandMessageXmd_batch(unsigned char* out, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len,
                                   size_t len_in_bytes, size_t n)
 {
     if (int rc = h2c_check_args(out, msg, msg_size, dst, dst_len, len_in_bytes)) return rc;
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ msg, nullptr, msg_size }, Arr{ nullptr, out, len_in_bytes } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return c25519_ExpandMessageXmd_dev(d[1], d[0], msg_size, dst, dst_len, len_in_bytes, c, st);
-                     });
+    return row_call(n, { Out(out, len_in_bytes), In(msg, msg_size) }, c25519_ExpandMessageXmd_dev, msg_size, dst, dst_len, len_in_bytes);
 }
 
 int ed25519_MapToCurve_batch(unsigned char* p, const unsigned char* u, size_t n)
 {
-    if (!p || !u) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ u, nullptr, 32 }, Arr{ nullptr, p, 32 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_MapToCurve_dev(d[1], d[0], c, st); });
+    return row_call(n, { Out(p, 32), In(u, 32) }, ed25519_MapToCurve_dev);
 }
 
 int ed25519_HashToCurve_batch(unsigned char* p, const unsigned char* msg, size_t msg_size, const unsigned char* dst, size_t dst_len, size_t n)
@@ -929,30 +825,19 @@ int ed25519_HashToScalar_batch(unsigned char* s, const unsigned char* msg, size_
 // ECVRF (engine_vrf.hip; csrc/vrf25519.cuh): alpha is staged like a signing call's messages
 int ed25519_VRF_Prove_batch(unsigned char* proof, const unsigned char* priv, const unsigned char* alpha, size_t alpha_size, size_t n)
 {
-    if (!proof || !priv || (!alpha && alpha_size)) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ priv, nullptr, 64 }, Arr{ alpha, nullptr, alpha_size }, Arr{ nullptr, proof, 80 } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_VRF_Prove_dev(d[2], d[0], d[1], alpha_size, c, st); });
+    return row_call(n, { Out(proof, 80), In(priv, 64), In(alpha, alpha_size) }, ed25519_VRF_Prove_dev, alpha_size);
 }
 
 int ed25519_VRF_Verify_batch(unsigned char* beta, int* ok, const unsigned char* pk, const unsigned char* proof, const unsigned char* alpha,
                              size_t alpha_size, size_t n)
 {
-    if (!beta || !ok || !pk || !proof || (!alpha && alpha_size)) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ pk, nullptr, 32 }, Arr{ proof, nullptr, 80 }, Arr{ alpha, nullptr, alpha_size }, Arr{ nullptr, beta, 64 },
-                          Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int {
-                         return ed25519_VRF_Verify_dev(d[3], d[4], d[0], d[1], d[2], alpha_size, c, st);
-                     });
+    return row_call(n, { Out(beta, 64), Out(ok, sizeof(int)), In(pk, 32), In(proof, 80), In(alpha, alpha_size) }, ed25519_VRF_Verify_dev,
+                    alpha_size);
 }
 
 int ed25519_VRF_ProofToHash_batch(unsigned char* beta, int* ok, const unsigned char* proof, size_t n)
 {
-    if (!beta || !ok || !proof) return bad_arg("null pointer");
-    if (n == 0) return 0;
-    return run_batch(n, { Arr{ proof, nullptr, 80 }, Arr{ nullptr, beta, 64 }, Arr{ nullptr, ok, sizeof(int) } },
-                     [&](void** d, size_t c, size_t, hipStream_t st) -> int { return ed25519_VRF_ProofToHash_dev(d[1], d[2], d[0], c, st); });
+    return row_call(n, { Out(beta, 64), Out(ok, sizeof(int)), In(proof, 80) }, ed25519_VRF_ProofToHash_dev);
 }
 
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace c25519_host {
@@ -521,6 +522,32 @@ int run_batch(size_t n, std::initializer_list<Arr> arrays, Launch launch, const 
     if (failed || resident_result) quiesce();
     if (failed) last_error() = failed_text;               // whichever thread saw it first: the caller gets rc AND text
     return failed;
+}
+
+// ---- a per-row call: the whole body of a *_batch wrapper whose *_dev form is (arrays..., values..., n, stream) ---------------------
+//     return row_call(n, { Out(shared, 32), In(pk, 32), InOut(sk, 32) }, curve25519_dh_CreateSharedKey_dev);
+// The arrays stand in the ORDER OF THE *_dev PROTOTYPE, each with its direction and row width; `pass` are the values between the
+// arrays and n (msg_size, dst, dst_len, ...).  From that one list come the null check (an array may be null exactly when its rows
+// are 0 bytes wide: msg with msg_size 0), n == 0, run_batch's list and the call on the staged pointers, so no wrapper indexes them
+// by hand.  `dev` is any callable of that shape; everything here is resolved at compile time.  (static: the lambda handed to run_batch
+// is then local to the translation unit, like a wrapper's own, and the library exports no instantiation of the pipeline.)
+inline Arr In(const void* p, size_t width) { return Arr{ p, nullptr, width }; }
+inline Arr Out(void* p, size_t width) { return Arr{ nullptr, p, width }; }
+inline Arr InOut(void* p, size_t width) { return Arr{ p, p, width }; }
+
+template <size_t... I, typename Dev, typename... Pass>
+static int row_call_at(std::index_sequence<I...>, size_t n, const Arr* rows, Dev dev, Pass... pass)
+{
+    return run_batch(n, { rows[I]... }, [&](void** d, size_t c, size_t, hipStream_t st) -> int { return dev(d[I]..., pass..., c, st); });
+}
+
+template <size_t K, typename Dev, typename... Pass>
+static int row_call(size_t n, const Arr (&rows)[K], Dev dev, Pass... pass)
+{
+    for (const Arr& a : rows)
+        if (!a.in && !a.out && a.elem) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    return row_call_at(std::make_index_sequence<K>{}, n, rows, dev, pass...);
 }
 
 // ---- ragged host calls: message i is msgs[offsets[i] .. offsets[i+1]), offsets has n + 1 entries (host memory) -----------

@@ -14,16 +14,35 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADERS = ("curve25519_dh.h", "ed25519_signature.h", "curve25519_amd.h")
+PREFIXES = ("curve25519_", "ed25519_", "c25519_", "ristretto255_")
+
+
 def declared_functions():
     names = set()
-    for h in ("curve25519_dh.h", "ed25519_signature.h", "curve25519_amd.h"):
+    for h in HEADERS:
         text = open(os.path.join(ROOT, "include", h)).read()
         text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
         for m in re.finditer(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\(", text):
             name = m.group(1)
-            if name.startswith(("curve25519_", "ed25519_", "c25519_")):
+            if name.startswith(PREFIXES):
                 names.add(name)
     return sorted(names)
+
+
+def declared_prototypes():
+    """{name: [parameter text, ...]} of every function the three headers declare (`(void)` is no parameter)"""
+    protos = {}
+    for h in HEADERS:
+        text = open(os.path.join(ROOT, "include", h)).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        text = re.sub(r"//[^\n]*|^\s*#[^\n]*", "", text, flags=re.M)
+        for m in re.finditer(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^()]*)\)\s*;", text):
+            name, params = m.group(1), " ".join(m.group(2).split())
+            if name.startswith(PREFIXES):
+                assert name not in protos, f"{name} is declared twice"
+                protos[name] = [] if params in ("", "void") else [p.strip() for p in params.split(",")]
+    return protos
 
 
 def test_headers_declare_the_reference_api():
@@ -53,6 +72,19 @@ def test_library_exports_every_declared_symbol():
     for n in (64, 65, 1 << 20):
         words = n * 640 + 4 * r4(10 * n) + r4(14 * n) + 2 * r4(5 * n) + 5 * r4(n) + 4
         assert lib.ed25519_VerifySignature_scratch_bytes(n) == 4 * words
+
+
+def test_ctypes_signatures_match_the_prototypes():
+    """every declared function: as many argtypes as the prototype has parameters, and a pointer type exactly where the parameter
+    has a `*` -- a missing size_t in the table is a wrong call, not an error"""
+    from curve25519_amd import _lib
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions() and len(protos) >= 180
+    for name, params in protos.items():
+        argtypes = _lib.SIGNATURES[name]
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            assert (t in (C.c_void_p, C.c_char_p)) == ("*" in p), (name, i, p, t)
 
 
 def test_headers_compile_as_c_and_cxx(tmp_path):
