@@ -274,6 +274,14 @@ struct GrowArray {
     }
 };
 
+// the words of a work slab's report buffer (ThreadState::report_word_for) and the call that owns each
+enum ReportWord {
+    REPORT_SLOW_ELEMENTS,       // ed25519_VerifySignature_*: how many elements the reference-order kernel decided (engine_verify.hip)
+    REPORT_LADDER_ELEMENTS,     // curve25519_dh_CreateSharedKey_indexed_*: how many elements ran the ladder (engine_x25519.hip)
+    REPORT_WIDE_OK,             // ed25519_Verify_Check_*: non-zero = the two wide combs decide this batch (engine_verify_ctx.hip)
+    REPORT_WORDS
+};
+
 // Per-host-thread device resources.  The staging side (streams, pinned + device buffers of the *_batch pipeline)
 // belongs to ONE device (`device`): when the thread calls a *_batch function with another current device, the old
 // device's staging is released first, on that device.  Work scratch of the *_dev functions is kept per device.
@@ -328,7 +336,7 @@ struct ThreadState {
     WorkSlab work[MAX_DEV][CALLER_SLABS];
     unsigned long work_clock = 0;
     unsigned long generation = 0;          // bumped whenever streams / slabs / report words are destroyed: a handle to one of
-                                           // them remembered across calls (engine.hip: LastVerify) is stale afterwards
+                                           // them remembered across calls (LastCall below) is stale afterwards
     // per device and use: a buffer whose CONTENT outlives the call -- KEEP_VERIFY the comb of the last one-key verification
     // batch's key, KEEP_PEER the comb of the last one-peer X25519 batch's peer key (engine.hip) -- so that the two do not evict
     // each other; same stream-order rules as a work slab
@@ -472,8 +480,9 @@ struct ThreadState {
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return false;
         return keep[dev][slot].ptr != nullptr;
     }
-    // the report word of the slab acquire_work(…, s) handed out (call between acquire_work and release_work)
-    int report_word_for(unsigned** out, hipStream_t s)
+    // a report word of the slab that acquire_work(…, s) hands out: each kind of call that reports has a word of its own (ReportWord),
+    // which no call's scratch overlaps, so the word is still the call's when later calls of other kinds have reused the slab
+    int report_word_for(unsigned** out, ReportWord which, hipStream_t s)
     {
         int dev = 0;
         C25519_TRY(hipGetDevice(&dev));
@@ -483,7 +492,7 @@ struct ThreadState {
             C25519_TRY(hipMalloc(&w.report, 256));
             C25519_RC(zero_device_now(w.report, 256));
         }
-        *out = w.report;
+        *out = w.report + which;
         return 0;
     }
     int release_work(hipStream_t s)
@@ -558,6 +567,43 @@ inline ThreadState& tls()
     return s;
 }
 
+// What a thread's last call of one kind left behind for its c25519_amd_*_last_* hook: a value the host knows already, or the device
+// word that the call's kernels report in (which wins), with the stream they run on.  The word and the stream die with the thread's
+// slabs: a bump of ThreadState::generation since the call makes the note stale.
+struct __attribute__((visibility("hidden"))) LastCall {
+    long host = -1;                        // -1: nothing to report
+    const unsigned* word = nullptr;
+    hipStream_t stream = nullptr;
+    int device = -1;
+    unsigned long generation = 0;
+    static LastCall known(long value)
+    {
+        LastCall c;
+        c.host = value;
+        c.generation = tls().generation;
+        return c;
+    }
+    void reports_in(const unsigned* w, hipStream_t s)
+    {
+        word = w; stream = s;
+        generation = tls().generation;
+        (void)hipGetDevice(&device);
+    }
+    // the value, or -1: nothing to report, c25519_amd_thread_release() or a device switch since, another current device than the
+    // call's.  Synchronises with the call's stream when the value is the device's.
+    long read() const
+    {
+        if (generation != tls().generation) return -1;
+        if (!word) return host;
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess || dev != device) return -1;
+        if (hipStreamSynchronize(stream) != hipSuccess) return -1;
+        unsigned v = 0;
+        if (hipMemcpy(&v, word, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return (long)v;
+    }
+};
+
 // A work slab between acquire_work and release_work.  Leaving the scope without release() -- an error return between the
 // two, with kernels possibly queued on the slab already -- still records the slab's `done` event on the stream, so that a
 // stream that takes the slab over later waits for everything that was enqueued, not for a stale event.
@@ -573,8 +619,9 @@ public:
         stream_ = s; live_ = true;
         return 0;
     }
-    int release()
+    int release()                          // (idle: a call that ran on scratch its caller holds has nothing to release)
     {
+        if (!live_) return 0;
         live_ = false;
         return tls().release_work(stream_);
     }

@@ -8,7 +8,7 @@
 #include <cerrno>
 #include <sys/random.h>
 
-// scratch of one equation, carved from the calling thread's slab (batcheq_carve): n elements, N = 2n points (keys, then R's),
+// scratch of one equation, cut from the calling thread's slab (batcheq_layout): n elements, N = 2n points (keys, then R's),
 // K = (wa + 1) * buckets counters (the windows of buckets: msm25519.cuh, MsmShape)
 struct BatchEqScratch {
     u32* rows;              // [N][32]  packed row of -P (msm_point_row), 128-byte aligned
@@ -258,7 +258,7 @@ __global__ void __launch_bounds__(BE_AND_BLOCK) k_ed25519_batcheq_and(int* resul
 }
 
 // ---- the coalesced equation (ed25519_VerifyBatch_zip215_indexed_*): n elements name K keys, N = K + n points (the keys, then the R's).
-// BatchEqScratch carved for that shape (keyeq_carve): flags has one word per POINT -- a key's: it does not decode, or its scalar is
+// BatchEqScratch cut for that shape (keyeq_layout): flags has one word per POINT -- a key's: it does not decode, or its scalar is
 // zero; an R's: its element is left out --, and keysum holds eight 64-bit sums per key.  The scan, the buckets, the windows and the
 // tail are the kernels above.
 
@@ -411,28 +411,27 @@ inline bool batcheq_for(size_t n)
 }
 inline size_t batcheq_blocks(size_t n) { return (n + BE_BLOCK - 1) / BE_BLOCK; }
 
-// words of the equation's scratch (the formula of include/curve25519_amd.h)
-inline size_t batcheq_words(size_t n, const BatchEqShape& sh)
+// the equation's scratch in slab order (its size is the formula of include/curve25519_amd.h); zeroed_words: flags, counts, cursor and
+// reject are one run, zeroed by one fill
+struct BatchEqParts { BatchEqScratch s; size_t zeroed_words; };
+inline BatchEqParts batcheq_layout(Carve& c, size_t n, const BatchEqShape& sh)
 {
     const size_t K = (size_t)(sh.wa + 1) * sh.buckets;
-    return 2 * n * (MSM_ROW_WORDS + 8) + (K + sh.wa + 1) * MSM_EXT_WORDS + n * (sh.wa + sh.wz) + 16 * batcheq_blocks(n) + round_up(n, 4) + 2 * K + 4;
-}
-
-inline BatchEqScratch batcheq_carve(u32* base, size_t n, const BatchEqShape& sh)
-{
-    const size_t K = (size_t)(sh.wa + 1) * sh.buckets;
-    BatchEqScratch s;
-    s.rows = base;
-    s.buckets = s.rows + 2 * n * MSM_ROW_WORDS;
-    s.windows = s.buckets + K * MSM_EXT_WORDS;
-    s.sc = s.windows + (size_t)(sh.wa + 1) * MSM_EXT_WORDS;
-    s.entries = s.sc + 16 * n;
-    s.partial = s.entries + n * (sh.wa + sh.wz);
-    s.flags = s.partial + 16 * batcheq_blocks(n);
-    s.counts = s.flags + round_up(n, 4);                     // flags, counts, cursor, reject: one run, zeroed by one fill
-    s.cursor = s.counts + K;
-    s.reject = s.cursor + K;
-    return s;
+    BatchEqParts p;
+    BatchEqScratch& s = p.s;
+    s.rows = c.take(2 * n * MSM_ROW_WORDS);
+    s.buckets = c.take(K * MSM_EXT_WORDS);
+    s.windows = c.take((size_t)(sh.wa + 1) * MSM_EXT_WORDS);
+    s.sc = c.take(16 * n);
+    s.entries = c.take(n * (sh.wa + sh.wz));
+    s.partial = c.take(16 * batcheq_blocks(n));
+    const size_t run = c.words();
+    s.flags = c.take4(n);
+    s.counts = c.take(K);
+    s.cursor = c.take(K);
+    s.reject = c.take(4);                                    // one word used
+    p.zeroed_words = c.words() - run;
+    return p;
 }
 
 thread_local long tl_batch_last_equation = -1;
@@ -445,11 +444,11 @@ int batcheq_equation(int* result, void* point_out, const void* sig, const void* 
     C25519_RC(wide_tables(&wide));
     const BatchEqShape sh = batcheq_shape(n);
     const unsigned K = (unsigned)((sh.wa + 1) * sh.buckets);
-    void* w = nullptr;
+    BatchEqParts parts;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, batcheq_words(n, sh) * sizeof(u32), stream));
-    const BatchEqScratch s = batcheq_carve((u32*)w, n, sh);
-    C25519_TRY(hipMemsetAsync(s.flags, 0, (round_up(n, 4) + 2 * (size_t)K + 4) * sizeof(u32), stream));
+    C25519_RC(lease_scratch(&parts, lease, stream, [&](Carve& c) { return batcheq_layout(c, n, sh); }));
+    const BatchEqScratch& s = parts.s;
+    C25519_TRY(hipMemsetAsync(s.flags, 0, parts.zeroed_words * sizeof(u32), stream));
     k_ed25519_batcheq_points<<<grid_for(2 * n, ED_BLOCK), ED_BLOCK, 0, stream>>>(s, sig, pk, n);
     C25519_TRY(hipGetLastError());
     const unsigned blocks = (unsigned)batcheq_blocks(n);
@@ -474,19 +473,28 @@ int batcheq_equation(int* result, void* point_out, const void* sig, const void* 
     return lease.release();
 }
 
-// below BATCH_EQ_MIN: ed25519_VerifySignature_zip215_dev into the slab behind that call's own scratch (it leases the same slab from
-// its first byte), then the AND
+// the per-element paths' scratch: ed25519_VerifySignature_zip215_dev's own, which that call runs on, then the verdicts, the AND's two
+// state words and, for the coalesced call, the n gathered keys
+struct PerElementScratch { u32* inner; int* verdict; u32 *state, *pk; };
+inline PerElementScratch per_element_layout(Carve& c, size_t n, bool gathered_keys)
+{
+    PerElementScratch p;
+    p.inner = inner_verify_scratch(c, n);
+    p.verdict = (int*)c.take4(n);
+    p.state = c.take(4);                                     // two words used
+    p.pk = c.take(gathered_keys ? 8 * n : 0);
+    return p;
+}
+
+// below BATCH_EQ_MIN: ed25519_VerifySignature_zip215_dev, then the AND
 int batcheq_per_element(int* result, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream)
 {
-    const size_t inner = round_up(ed25519_VerifySignature_scratch_bytes(n), 256);
-    void* w = nullptr;
+    PerElementScratch p;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, inner + round_up(n, 4) * sizeof(int) + 16, stream));
-    int* verdict = (int*)((char*)w + inner);
-    u32* state = (u32*)(verdict + round_up(n, 4));
-    C25519_TRY(hipMemsetAsync(state, 0, 2 * sizeof(u32), stream));
-    C25519_RC(verify_dev(verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false));   // the AND below is
-    k_ed25519_batcheq_and<<<std::min(grid_for(n, BE_AND_BLOCK), 256u), BE_AND_BLOCK, 0, stream>>>(result, verdict, n, state);
+    C25519_RC(lease_scratch(&p, lease, stream, [n](Carve& c) { return per_element_layout(c, n, false); }));
+    C25519_TRY(hipMemsetAsync(p.state, 0, 2 * sizeof(u32), stream));
+    C25519_RC(verify_dev(p.verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false, p.inner));   // the AND below is
+    k_ed25519_batcheq_and<<<std::min(grid_for(n, BE_AND_BLOCK), 256u), BE_AND_BLOCK, 0, stream>>>(result, p.verdict, n, p.state);
     C25519_TRY(hipGetLastError());
     return lease.release();
 }
@@ -541,32 +549,27 @@ inline bool keyeq_for(size_t n)
     return mn > 0 && n >= (size_t)mn;
 }
 
-// words of the coalesced equation's scratch (the formula of include/curve25519_amd.h)
-inline size_t keyeq_words(size_t n, size_t K, const BatchEqShape& sh)
-{
-    const size_t KB = (size_t)(sh.wa + 1) * sh.buckets, N = K + n;
-    return N * (MSM_ROW_WORDS + 8) + (KB + sh.wa + 1) * MSM_EXT_WORDS + n * sh.wz + K * sh.wa + 16 * batcheq_blocks(n) + 16 * K + round_up(N, 4) + 2 * KB + 4;
-}
-
+// the coalesced equation's scratch in slab order (its size is the formula of include/curve25519_amd.h); zeroed_words: keysum, flags,
+// counts, cursor and reject are one run, zeroed by one fill
 struct KeyEqScratch { BatchEqScratch s; unsigned long long* keysum; size_t zeroed_words; };
-inline KeyEqScratch keyeq_carve(u32* base, size_t n, size_t K, const BatchEqShape& sh)
+inline KeyEqScratch keyeq_layout(Carve& c, size_t n, size_t K, const BatchEqShape& sh)
 {
     const size_t KB = (size_t)(sh.wa + 1) * sh.buckets, N = K + n;
     KeyEqScratch k;
     BatchEqScratch& s = k.s;
-    s.rows = base;
-    s.buckets = s.rows + N * MSM_ROW_WORDS;
-    s.windows = s.buckets + KB * MSM_EXT_WORDS;
-    s.sc = s.windows + (size_t)(sh.wa + 1) * MSM_EXT_WORDS;
-    s.partial = s.sc + 8 * N;
-    u32* sums = s.partial + 16 * batcheq_blocks(n);          // (an even number of words from the slab's start: 64-bit sums)
-    k.keysum = reinterpret_cast<unsigned long long*>(sums);
-    s.flags = sums + 16 * K;                                 // keysum, flags, counts, cursor, reject: one run, zeroed by one fill
-    s.counts = s.flags + round_up(N, 4);
-    s.cursor = s.counts + KB;
-    s.reject = s.cursor + KB;
-    s.entries = s.reject + 4;
-    k.zeroed_words = 16 * K + round_up(N, 4) + 2 * KB + 4;
+    s.rows = c.take(N * MSM_ROW_WORDS);
+    s.buckets = c.take(KB * MSM_EXT_WORDS);
+    s.windows = c.take((size_t)(sh.wa + 1) * MSM_EXT_WORDS);
+    s.sc = c.take(8 * N);
+    s.partial = c.take(16 * batcheq_blocks(n));
+    const size_t run = c.words();
+    k.keysum = reinterpret_cast<unsigned long long*>(c.take(16 * K));   // (an even number of words from the slab's start: 64-bit sums)
+    s.flags = c.take4(N);
+    s.counts = c.take(KB);
+    s.cursor = c.take(KB);
+    s.reject = c.take(4);                                    // one word used
+    k.zeroed_words = c.words() - run;
+    s.entries = c.take(n * sh.wz + K * sh.wa);
     return k;
 }
 
@@ -579,10 +582,9 @@ int keyeq_equation(int* result, void* point_out, const void* keys, size_t K, con
     const BatchEqShape sh = batcheq_shape(n);
     const unsigned KB = (unsigned)((sh.wa + 1) * sh.buckets);
     const size_t N = K + n;
-    void* w = nullptr;
+    KeyEqScratch k;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, keyeq_words(n, K, sh) * sizeof(u32), stream));
-    const KeyEqScratch k = keyeq_carve((u32*)w, n, K, sh);
+    C25519_RC(lease_scratch(&k, lease, stream, [&](Carve& c) { return keyeq_layout(c, n, K, sh); }));
     const BatchEqScratch& s = k.s;
     C25519_TRY(hipMemsetAsync(k.keysum, 0, k.zeroed_words * sizeof(u32), stream));
     k_ed25519_keyeq_points<<<grid_for(N, ED_BLOCK), ED_BLOCK, 0, stream>>>(s, sig, keys, K, n);
@@ -612,18 +614,14 @@ int keyeq_equation(int* result, void* point_out, const void* keys, size_t K, con
 // below BATCH_EQ_INDEXED_MIN: the keys gathered behind batcheq_per_element's layout, then that path
 int keyeq_per_element(int* result, const void* keys, size_t K, const void* key_index, const void* sig, Msgs msgs, size_t n, hipStream_t stream)
 {
-    const size_t inner = round_up(ed25519_VerifySignature_scratch_bytes(n), 256);
-    void* w = nullptr;
+    PerElementScratch p;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, inner + round_up(n, 4) * sizeof(int) + 16 + n * 32, stream));
-    int* verdict = (int*)((char*)w + inner);
-    u32* state = (u32*)(verdict + round_up(n, 4));
-    void* pk = state + 4;
-    C25519_TRY(hipMemsetAsync(state, 0, 2 * sizeof(u32), stream));
-    k_ed25519_keyeq_gather<<<grid_for(n, BE_BLOCK), BE_BLOCK, 0, stream>>>(pk, keys, (const u32*)key_index, n, K, state);
+    C25519_RC(lease_scratch(&p, lease, stream, [n](Carve& c) { return per_element_layout(c, n, true); }));
+    C25519_TRY(hipMemsetAsync(p.state, 0, 2 * sizeof(u32), stream));
+    k_ed25519_keyeq_gather<<<grid_for(n, BE_BLOCK), BE_BLOCK, 0, stream>>>(p.pk, keys, (const u32*)key_index, n, K, p.state);
     C25519_TRY(hipGetLastError());
-    C25519_RC(verify_dev(verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false));
-    k_ed25519_batcheq_and<<<std::min(grid_for(n, BE_AND_BLOCK), 256u), BE_AND_BLOCK, 0, stream>>>(result, verdict, n, state);
+    C25519_RC(verify_dev(p.verdict, sig, p.pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false, p.inner));
+    k_ed25519_batcheq_and<<<std::min(grid_for(n, BE_AND_BLOCK), 256u), BE_AND_BLOCK, 0, stream>>>(result, p.verdict, n, p.state);
     C25519_TRY(hipGetLastError());
     return lease.release();
 }
@@ -659,7 +657,7 @@ int keyeq_dev(void* result, const void* keys, size_t n_key, const void* key_inde
 
 extern "C" {
 
-size_t ed25519_VerifyBatch_scratch_bytes(size_t n) { return batcheq_words(n, batcheq_shape(n)) * sizeof(u32); }
+size_t ed25519_VerifyBatch_scratch_bytes(size_t n) { return layout_bytes([n](Carve& c) { return batcheq_layout(c, n, batcheq_shape(n)); }); }
 
 long c25519_amd_verify_batch_last_equation(void) { return tl_batch_last_equation; }
 
@@ -773,7 +771,10 @@ int ed25519_VerifyBatch_zip215_ragged_batch(int* all_valid, int* verdict, const 
 
 // ---- the coalesced forms: keys[key_index[i]] is element i's key ----
 
-size_t ed25519_VerifyBatch_indexed_scratch_bytes(size_t n, size_t n_key) { return keyeq_words(n, n_key, batcheq_shape(n)) * sizeof(u32); }
+size_t ed25519_VerifyBatch_indexed_scratch_bytes(size_t n, size_t n_key)
+{
+    return layout_bytes([=](Carve& c) { return keyeq_layout(c, n, n_key, batcheq_shape(n)); });
+}
 
 int ed25519_VerifyBatch_zip215_indexed_dev(void* result, const void* keys, size_t n_key, const void* key_index, const void* sig,
                                            const void* msg, size_t msg_size, size_t n, const unsigned char* seed, void* stream)

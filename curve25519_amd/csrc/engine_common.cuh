@@ -30,6 +30,7 @@
 #pragma once
 #include "capi_common.hpp"
 #include "host_pipeline.hpp"
+#include "scratch_carve.hpp"
 #include "lanes.cuh"
 #include "verify_fast.cuh"
 #include "coop25519.cuh"
@@ -51,11 +52,8 @@
 
 using namespace c25519;
 
-// per-call scratch, carved out of one slab (all sizes in u32 words per element)
-constexpr size_t SCR_FE = 10;
-struct ProjScratch {            // projective result + prefix products of the batched inversion
-    u32 *a, *b, *z, *prefix;    // X25519 public_fast: a = numerator, z = denominator.  Edwards: a = X, b = Y, z = Z.
-};
+// per-call scratch is one lease of the calling thread's slab, sized and cut by ONE layout function per scratch shape (scratch_carve.hpp:
+// Carve, and ProjScratch, the projective part most shapes begin with; lease_scratch below runs the layout twice)
 
 // lanes per workgroup of the Ed25519 batch kernels (and waves per SIMD their register allocation aims at)
 #ifndef C25519_ED_BLOCK
@@ -176,6 +174,7 @@ __global__ void __launch_bounds__(INV_BLOCK) __attribute__((amdgpu_waves_per_eu(
 namespace c25519_engine {
 
 using c25519_host::Arr;
+using c25519_host::Carve;
 using c25519_host::ThreadState;
 using c25519_host::aligned16;
 using c25519_host::round_up;
@@ -206,8 +205,10 @@ int sign_dev(void* sig, const void* priv, const void* blinding, Msgs msgs, size_
 // the *_zip215 ones (cofactored equation, any point encoding, S < L) with their own kernel for the slow list
 enum VerifyRules { RULES_PLAIN, RULES_STRICT, RULES_ZIP215 };
 // last_in_call = false: more kernels of the same call follow (the AND of ed25519_VerifyBatch_zip215_*), so a call of ONE element's
-// completion word is not this call's to signal
-int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules, bool last_in_call = true);
+// completion word is not this call's to signal.  work: null, or scratch of ed25519_VerifySignature_scratch_bytes(n) bytes the caller
+// holds already on this stream (the first part of its own layout: the tables want the slab's alignment); then nothing is leased
+int verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules, bool last_in_call = true,
+               u32* work = nullptr);
 
 // the messages of a call: n of msg_size bytes each, or message i at msgs[offsets[i] .. offsets[i+1])
 inline Msgs fixed_msgs(const void* msg, size_t msg_size) { return Msgs{ (const uint8_t*)msg, msg_size, nullptr }; }
@@ -217,13 +218,38 @@ inline unsigned grid_for(size_t n, int block) { return (unsigned)((n + block - 1
 // the wide comb is the default: sign 824 against 643 M/s, key pairs 1110 against 815 M/s at 2^20 (profiles/r05_ab_base_comb.txt)
 inline bool base_comb_wide() { return c25519_host::tunable_or(c25519_host::T_BASE_COMB, 1) == 1; }
 
-// words of the projective-result part of the scratch for n elements (a, b, z, prefix; 16-byte aligned parts)
-inline size_t proj_words(size_t n) { return 4 * round_up(SCR_FE * n, 4); }
-
-inline ProjScratch carve_proj(u32* base, size_t n)
+// The scratch of a call: `layout` (a function of a Carve& that returns the call's struct of pointers) is run once without a base to size
+// the lease and once on the leased slab.  held: null, or scratch the caller holds already on this stream (a call that runs inside
+// another call's lease: the caller's own layout took this call's sizing pass); then nothing is leased and `lease` stays idle.
+template <typename Layout>
+size_t layout_bytes(Layout layout)
 {
-    const size_t part = round_up(SCR_FE * n, 4);
-    return ProjScratch{ base, base + part, base + 2 * part, base + 3 * part };
+    Carve size;
+    layout(size);
+    return size.bytes();
+}
+template <typename Scratch, typename Layout>
+int lease_scratch(Scratch* out, c25519_host::WorkLease& lease, hipStream_t stream, Layout layout, u32* held = nullptr)
+{
+    void* w = held;
+    if (!held) C25519_RC(lease.acquire(&w, layout_bytes(layout), stream));
+    Carve cut(w);
+    *out = layout(cut);
+    return 0;
+}
+// ... of the commonest shape, the projective part alone
+static inline int lease_proj(ProjScratch* out, c25519_host::WorkLease& lease, size_t n, hipStream_t stream, u32* held = nullptr)
+{
+    return lease_scratch(out, lease, stream, [n](Carve& c) { return c.proj(n); }, held);
+}
+// A call that runs the per-element verification inside its own lease begins its layout with that call's scratch (verify_dev's `work`;
+// first in the slab, as the tables want it) and has its own parts follow on the next 256-byte boundary.  No function leases a slab
+// while its caller holds it: an inner request above the slab's capacity would free what the outer call is using.
+static inline u32* inner_verify_scratch(Carve& c, size_t n)
+{
+    u32* inner = c.take(ed25519_VerifySignature_scratch_bytes(n) / sizeof(u32));
+    c.align(256);
+    return inner;
 }
 
 // how many elements share one inversion: as many as possible while every SIMD still gets a wave

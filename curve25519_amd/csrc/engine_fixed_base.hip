@@ -482,10 +482,9 @@ int curve25519_dh_CalculatePublicKey_fast_dev(void* pk, void* sk, size_t n, void
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    void* w = nullptr;
+    ProjScratch scr;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
+    C25519_RC(lease_proj(&scr, lease, n, stream));
     note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
@@ -528,10 +527,9 @@ int c25519_engine::keypair_dev(void* pub, void* priv, const void* sk, const void
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    void* w = nullptr;
+    ProjScratch scr;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
+    C25519_RC(lease_proj(&scr, lease, n, stream));
     note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
@@ -564,6 +562,19 @@ int ed25519_CreateKeyPair_blinded_dev(void* pub, void* priv, const void* blindin
 }
 
 }  // extern "C"
+
+// the scratch of a signing pass: the projective R, then 8 n words per scalar the finish kernel takes -- the key's half a (sign_dev: the
+// indexed call reads it from its context) and the nonce r
+struct SignScratch { ProjScratch scr; u32 *a_buf, *r_buf; };
+static SignScratch sign_layout(Carve& c, size_t n, bool with_a)
+{
+    SignScratch s;
+    s.scr = c.proj(n);
+    s.a_buf = with_a ? c.take4(8 * n) : nullptr;
+    s.r_buf = c.take4(8 * n);
+    return s;
+}
+
 int c25519_engine::sign_dev(void* sig, const void* priv, const void* blinding, Msgs msgs, size_t n, hipStream_t stream)
 {
     if (int rc = check_dev_args(n, { sig, priv, blinding })) return rc;
@@ -590,13 +601,10 @@ int c25519_engine::sign_dev(void* sig, const void* priv, const void* blinding, M
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    void* w = nullptr;
-    const size_t sc_words = round_up(8 * n, 4);
+    SignScratch ss;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, (proj_words(n) + 2 * sc_words) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
-    u32* a_buf = (u32*)w + proj_words(n);
-    u32* r_buf = a_buf + sc_words;
+    C25519_RC(lease_scratch(&ss, lease, stream, [n](Carve& c) { return sign_layout(c, n, true); }));
+    const auto& [scr, a_buf, r_buf] = ss;
     note_shape(SHAPE_LANE_INVERT, wide_comb ? (unsigned)WB_BLOCK : bm_block_for(n));
     if (wide_comb) {
         const u32* wide = nullptr;
@@ -687,12 +695,11 @@ static int sign_indexed_dev(void* sig, const void* ctxs_, size_t n_ctx, const vo
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    void* w = nullptr;
-    const size_t sc_words = round_up(8 * n, 4);
+    SignScratch ss;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, (proj_words(n) + sc_words) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
-    u32* r_buf = (u32*)w + proj_words(n);
+    C25519_RC(lease_scratch(&ss, lease, stream, [n](Carve& c) { return sign_layout(c, n, false); }));
+    const ProjScratch& scr = ss.scr;
+    u32* const r_buf = ss.r_buf;
     if (wide_comb) {
         const u32* wide = nullptr;
         C25519_RC(wide_tables(&wide));

@@ -60,20 +60,17 @@ __global__ void __launch_bounds__(EG_BLOCK, 2) k_ed25519_group_add(ProjScratch s
 
 namespace {
 
-// the scratch of a call with an ok word per element: the projective part, then n words
-struct GroupScratch {
-    c25519_host::WorkLease lease;
-    ProjScratch scr;
-    u32* okw = nullptr;
-    int acquire(size_t n, bool ok_words, hipStream_t stream)
-    {
-        void* w = nullptr;
-        C25519_RC(lease.acquire(&w, (proj_words(n) + (ok_words ? round_up(n, 4) : 0)) * sizeof(u32), stream));
-        scr = carve_proj((u32*)w, n);
-        okw = (u32*)w + proj_words(n);
-        return 0;
-    }
-};
+// the scratch of a call: the projective part, then (a call with an ok word per element) n words
+struct GroupScratch { ProjScratch scr; u32* okw; };
+int lease_group(GroupScratch* g, c25519_host::WorkLease& lease, size_t n, bool ok_words, hipStream_t stream)
+{
+    return lease_scratch(g, lease, stream, [=](Carve& c) {
+        GroupScratch s;
+        s.scr = c.proj(n);
+        s.okw = c.take4(ok_words ? n : 0);
+        return s;
+    });
+}
 
 // tunable SCALARMULT_WINDOW: 2, 3 or 4; anything else is the built-in choice
 int scalarmult_window()
@@ -90,7 +87,8 @@ int scalarmult_dev(void* q, void* ok, const void* scalar, const void* point, siz
     if (n == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     GroupScratch g;
-    C25519_RC(g.acquire(n, true, stream));
+    c25519_host::WorkLease lease;
+    C25519_RC(lease_group(&g, lease, n, true, stream));
     const unsigned grid = grid_for(n, EG_BLOCK);
     const u32 cm = clamp ? 0xffffffffu : 0u;
     switch (scalarmult_window()) {
@@ -100,7 +98,7 @@ int scalarmult_dev(void* q, void* ok, const void* scalar, const void* point, siz
     }
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(g.scr, n, FinishGroupPoint{ g.scr.a, g.scr.b, g.okw, q, n }, stream));
-    return g.lease.release();
+    return lease.release();
 }
 
 int scalarmult_base_dev(void* q, const void* scalar, size_t n, void* stream_, bool clamp)
@@ -113,11 +111,12 @@ int scalarmult_base_dev(void* q, const void* scalar, size_t n, void* stream_, bo
     const u32* wide = nullptr;
     C25519_RC(wide_tables(&wide));
     GroupScratch g;
-    C25519_RC(g.acquire(n, false, stream));
+    c25519_host::WorkLease lease;
+    C25519_RC(lease_group(&g, lease, n, false, stream));
     k_ed25519_group_base<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(g.scr, scalar, clamp ? 0xffffffffu : 0u, n, wide);
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(g.scr, n, FinishPack{ g.scr.a, g.scr.b, q, n, 1, 0, nullptr, 0, 0 }, stream));
-    return g.lease.release();
+    return lease.release();
 }
 
 int point_add_dev(void* r, void* ok, const void* p, const void* q, size_t n, void* stream_, bool sub)
@@ -128,11 +127,12 @@ int point_add_dev(void* r, void* ok, const void* p, const void* q, size_t n, voi
     if (n == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     GroupScratch g;
-    C25519_RC(g.acquire(n, true, stream));
+    c25519_host::WorkLease lease;
+    C25519_RC(lease_group(&g, lease, n, true, stream));
     k_ed25519_group_add<<<grid_for(n, EG_BLOCK), EG_BLOCK, 0, stream>>>(g.scr, g.okw, (int*)ok, p, q, sub ? 0xffffffffu : 0u, n);
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(g.scr, n, FinishGroupPoint{ g.scr.a, g.scr.b, g.okw, r, n }, stream));
-    return g.lease.release();
+    return lease.release();
 }
 
 }  // namespace

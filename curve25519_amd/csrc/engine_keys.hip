@@ -61,10 +61,9 @@ int ed25519_PublicKey_to_X25519_dev(void* xpk, void* ok, const void* pk, size_t 
     if (int rc = check_dev_args(n, { xpk, ok, pk })) return rc;
     if (n == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
-    void* w = nullptr;
+    ProjScratch scr;                                          // a = 1 + y, z = 1 - y, b = the ok words (n of its 10 n)
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);           // a = 1 + y, z = 1 - y, b = the ok words (n of its 10 n)
+    C25519_RC(lease_proj(&scr, lease, n, stream));
     k_ed25519_key_to_x25519<<<grid_for(n, EK_BLOCK), EK_BLOCK, 0, stream>>>(scr, (int*)ok, pk, n);
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(scr, n, FinishKeyX25519{ scr.a, scr.b, xpk, n }, stream));

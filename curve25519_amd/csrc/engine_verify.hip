@@ -495,15 +495,29 @@ namespace {
 // the fast path's scalars, flags and slow list
 constexpr size_t VERIFY_TABLE_WORDS = FAST_TABLE_WORDS > QTABLE_LIMB_WORDS ? FAST_TABLE_WORDS : QTABLE_LIMB_WORDS;
 static_assert(FAST_TABLE_WORDS % 32 == 0 && VERIFY_TABLE_WORDS % 32 == 0, "per-lane tables must keep their rows 128-byte aligned");
-inline size_t verify_scalar_words(size_t n) { return round_up(SIGMA_WORDS * n, 4) + 2 * round_up(5 * n, 4) + 5 * round_up(n, 4) + 4; }
-inline size_t verify_scratch_bytes(size_t n)
+constexpr size_t SLOW_COUNTERS = 3;          // FastScratch::slow_count: the count, then how many elements `order` holds from its front / its back
+struct VerifyScratch { u32* tables; ProjScratch scr; FastScratch fs; };
+inline VerifyScratch verify_layout(Carve& c, size_t n)
 {
-    return (n * VERIFY_TABLE_WORDS + proj_words(n) + verify_scalar_words(n)) * sizeof(u32);
+    VerifyScratch v;
+    FastScratch& fs = v.fs;
+    fs.tables = v.tables = c.take(n * VERIFY_TABLE_WORDS);  // first in the slab (hipMalloc: 256-byte aligned): packed rows are whole 128-byte lines
+    v.scr = c.proj(n);
+    fs.sigma = c.take4(SIGMA_WORDS * n);
+    fs.rho = c.take4(5 * n);
+    fs.tau = c.take4(5 * n);
+    fs.flags = c.take4(n);
+    fs.slow_list = c.take4(n);
+    fs.order = c.take4(n);
+    fs.slow_count = c.take4(SLOW_COUNTERS);
+    fs.pflags = c.take(2 * round_up(n, 4));                 // key lanes, then R lanes: 2n words are indexed (R of e at n + e)
+    fs.slow_report = nullptr;
+    fs.lat_cap_bits = LAT_CAP_BITS;
+    return v;
 }
 
 // what the calling thread's last fast-path verification left behind for c25519_amd_verify_last_slow_elements
-struct LastVerify { const u32* count = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; };
-thread_local LastVerify tl_last_verify;
+thread_local c25519_host::LastCall tl_last_verify;
 
 // fast = true: the lattice path (verify_fast.cuh) decides every element whose key is on the curve and whose short vector
 // fits; the reference's order runs for the others in a kernel of its own behind the walk.  fast = false: reference order for everything,
@@ -511,37 +525,27 @@ thread_local LastVerify tl_last_verify;
 // rules (fast only): engine_common.cuh: VerifyRules
 template <typename MakeFin>
 int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, int* verdict, bool fast, MakeFin make_fin,
-               VerifyRules rules = RULES_PLAIN, bool last_in_call = true)
+               VerifyRules rules = RULES_PLAIN, bool last_in_call = true, u32* work = nullptr)
 {
     const bool strict = rules == RULES_STRICT, zip215 = rules == RULES_ZIP215;
     const u32* tbl = nullptr;
     C25519_RC(base_tables(&tbl, nullptr));
-    void* w = nullptr;
+    VerifyScratch v;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, verify_scratch_bytes(n), stream));
-    u32* tables = (u32*)w;                                  // first in the slab (hipMalloc: 256-byte aligned): packed rows are
-    const ProjScratch scr = carve_proj(tables + n * VERIFY_TABLE_WORDS, n);   // whole 128-byte lines
+    C25519_RC(lease_scratch(&v, lease, stream, [n](Carve& c) { return verify_layout(c, n); }, work));
+    const ProjScratch& scr = v.scr;
     const unsigned grid = grid_for(n, ED_BLOCK);
     if (fast) {
         unsigned* report = nullptr;
-        C25519_RC(tls().report_word_for(&report, stream));
-        FastScratch fs;
-        fs.tables = tables;
-        fs.sigma = tables + n * VERIFY_TABLE_WORDS + proj_words(n);
-        fs.rho = fs.sigma + round_up(SIGMA_WORDS * n, 4);
-        fs.tau = fs.rho + round_up(5 * n, 4);
-        fs.flags = fs.tau + round_up(5 * n, 4);
-        fs.slow_list = fs.flags + round_up(n, 4);
-        fs.order = fs.slow_list + round_up(n, 4);
-        fs.slow_count = fs.order + round_up(n, 4);
-        fs.pflags = fs.slow_count + 4;
+        C25519_RC(tls().report_word_for(&report, c25519_host::REPORT_SLOW_ELEMENTS, stream));
+        FastScratch& fs = v.fs;
         fs.slow_report = report;
         {   // test knob: a lower cap sends ordinary signatures down the over-long-vector branch (slow list, reference order)
             const long cap = c25519_host::tunable_or(c25519_host::T_VERIFY_LAT_CAP_BITS, LAT_CAP_BITS);
             fs.lat_cap_bits = cap >= 100 && cap < LAT_CAP_BITS ? (int)cap : LAT_CAP_BITS;
         }
         if (!verify_quad_for(n) && verify_coop_for(n)) {   // a few elements: one launch, three waves per element
-            C25519_TRY(hipMemsetAsync(fs.slow_count, 0, 3 * sizeof(u32), stream));
+            C25519_TRY(hipMemsetAsync(fs.slow_count, 0, SLOW_COUNTERS * sizeof(u32), stream));
             note_shape(SHAPE_PER_GROUP, 192);
             (zip215 ? k_ed25519_verify_one_per_group_zip215 : strict ? k_ed25519_verify_one_per_group_strict : k_ed25519_verify_one_per_group)<<<(unsigned)n, 192, 0, stream>>>(
                 fs, verdict, sig, pk, msgs, n, tbl);
@@ -574,16 +578,14 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
         (zip215 ? k_ed25519_verify_slow_zip215 : k_ed25519_verify_slow)<<<grid, ED_BLOCK, 0, stream>>>(fs, verdict, sig, pk, msgs, tbl,
                                                                                                      last_in_call ? take_done_word(n) : DoneWord{ nullptr, 0 });
         C25519_TRY(hipGetLastError());
-        tl_last_verify.count = report; tl_last_verify.stream = stream;
-        tl_last_verify.generation = tls().generation;       // the report word and the stream die with the thread's slabs
-        (void)hipGetDevice(&tl_last_verify.device);
+        tl_last_verify.reports_in(report, stream);
         return lease.release();
     }
-    tl_last_verify = LastVerify();
+    tl_last_verify = c25519_host::LastCall();
     note_shape(SHAPE_LANE_INVERT, ED_BLOCK);
-    k_ed25519_verify_init<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(pk, n, tables, VERIFY_TABLE_WORDS);
+    k_ed25519_verify_init<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(pk, n, v.tables, VERIFY_TABLE_WORDS);
     C25519_TRY(hipGetLastError());
-    k_ed25519_verify_check<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(scr, sig, pk, msgs, n, tbl, tables, VERIFY_TABLE_WORDS);
+    k_ed25519_verify_check<QTableLimbs><<<grid, ED_BLOCK, 0, stream>>>(scr, sig, pk, msgs, n, tbl, v.tables, VERIFY_TABLE_WORDS);
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(scr, n, make_fin(scr), stream));
     return lease.release();
@@ -592,7 +594,7 @@ int verify_run(const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t
 }  // namespace
 
 int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Msgs msgs, size_t n, hipStream_t stream, VerifyRules rules,
-                              bool last_in_call)
+                              bool last_in_call, u32* work)
 {
     // tunable VERIFY_REFERENCE_ORDER = 1: every element through the reference-order kernels -- Verify_Init's 4-fold table per
     // key, then the 4-fold + 8-fold walk of ed25519_verify.c:243-280: BASELINE.json configs[3] as worded (A/B and test knob).
@@ -601,12 +603,12 @@ int c25519_engine::verify_dev(void* verdict, const void* sig, const void* pk, Ms
     if (int rc = check_dev_args(n, { verdict, sig, pk })) return rc;
     if (n == 0) return 0;
     return verify_run(sig, pk, msgs, n, stream, (int*)verdict, fast,
-                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules, last_in_call);
+                      [&](const ProjScratch& scr) { return FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, nullptr }; }, rules, last_in_call, work);
 }
 
 extern "C" {
 
-size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return verify_scratch_bytes(n); }
+size_t ed25519_VerifySignature_scratch_bytes(size_t n) { return layout_bytes([n](Carve& c) { return verify_layout(c, n); }); }
 
 // test hook: enc(T) instead of the verdict (what Verify_Check compares with enc(R)); device pointers
 int c25519_amd_verify_point_dev(void* out, const void* sig, const void* pk, const void* msg, size_t msg_size, size_t n,
@@ -625,14 +627,7 @@ int c25519_amd_verify_point_dev(void* out, const void* sig, const void* pk, cons
 long c25519_amd_verify_last_slow_elements(void)
 {
     C25519_API_CALL_OR(-1);
-    const LastVerify& lv = tl_last_verify;
-    int dev = -1;
-    if (!lv.count || hipGetDevice(&dev) != hipSuccess || dev != lv.device) return -1;
-    if (lv.generation != tls().generation) return -1;       // c25519_amd_thread_release() / a device switch freed what lv points at
-    if (hipStreamSynchronize(lv.stream) != hipSuccess) return -1;
-    u32 c = 0;
-    if (hipMemcpy(&c, lv.count, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (long)c;
+    return tl_last_verify.read();
 }
 
 int ed25519_VerifySignature_dev(void* verdict, const void* sig, const void* pk, const void* msg, size_t msg_size,

@@ -331,10 +331,8 @@ __global__ void __launch_bounds__(ZC_BLOCK) k_ed25519_verify_coset_index_mask(in
 namespace {
 
 // what the calling thread's last ed25519_Verify_Check_* call on this device left behind for c25519_amd_verify_check_last_wide:
-// where its "the two wide combs decide this batch" word lives (null: the call never asked) -- one of the slab's report words, which
-// no call's scratch overlaps: the word is the call's own and still there when later calls of other kinds have reused the slab
-struct LastCheck { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
-thread_local LastCheck tl_last_check;
+// 0 (the call never asked), or where its "the two wide combs decide this batch" word lives (the slab's REPORT_WIDE_OK)
+thread_local c25519_host::LastCall tl_last_check;
 
 }  // namespace
 
@@ -372,14 +370,17 @@ static int launch_coset_finish(const ProjScratch& scr, size_t n, const u32* ctxs
 static int zip215_check_gathered(int* verdict, const void* ctxs, size_t n_ctx, const void* ctx_index, const void* sig, Msgs msgs, size_t n,
                                  hipStream_t stream)
 {
-    const size_t inner = round_up(ed25519_VerifySignature_scratch_bytes(n), 256);
-    void* w = nullptr;
+    struct Gathered { u32 *inner, *pk; } g;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, inner + n * 32, stream));
-    void* pk = (char*)w + inner;
-    k_ed25519_verify_coset_key_gather<<<grid_for(n, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(pk, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
+    C25519_RC(lease_scratch(&g, lease, stream, [n](Carve& c) {
+        Gathered s;
+        s.inner = inner_verify_scratch(c, n);
+        s.pk = c.take(8 * n);                                // the n gathered keys
+        return s;
+    }));
+    k_ed25519_verify_coset_key_gather<<<grid_for(n, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(g.pk, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
     C25519_TRY(hipGetLastError());
-    C25519_RC(verify_dev(verdict, sig, pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false));
+    C25519_RC(verify_dev(verdict, sig, g.pk, msgs, n, stream, RULES_ZIP215, /* last_in_call = */ false, g.inner));
     if (ctx_index) {
         k_ed25519_verify_coset_index_mask<<<grid_for(n, ZC_BLOCK), ZC_BLOCK, 0, stream>>>(verdict, (const u32*)ctx_index, n_ctx, n);
         C25519_TRY(hipGetLastError());
@@ -424,18 +425,21 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
     const bool build = wide_from != 0 && n >= (size_t)wide_from;
     const bool reuse = !build && wide_from != 0 && !small && tls().has_keep();
     const bool try_wide = build || reuse;
-    tl_last_check = LastCheck();
-    tl_last_check.ran = true;
-    tl_last_check.generation = tls().generation;
+    tl_last_check = c25519_host::LastCall::known(0);
     if (!zip215 && !try_wide && small) {                    // a few pairs: one per wave, the reference's order
         k_ed25519_verify_check_coop<<<(unsigned)n, 64, 0, stream>>>((int*)verdict, sig, (const u32*)ctx, msgs, n, tbl, take_done_word(n));
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    void* w = nullptr;
+    struct CheckScratch { ProjScratch scr; u32* key_words; } cs;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, (proj_words(n) + 4) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
+    C25519_RC(lease_scratch(&cs, lease, stream, [n](Carve& c) {
+        CheckScratch s;
+        s.scr = c.proj(n);
+        s.key_words = c.take(4);                             // four words; the second one is rule 2 for the one context (ZIP-215)
+        return s;
+    }));
+    const ProjScratch& scr = cs.scr;
     u32* wide_ok = nullptr;
     bool quads = false;
     c25519_host::KeepLease keep_lease;                      // records the kept buffer's event however this call leaves
@@ -444,8 +448,8 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
         C25519_RC(wide_tables(&wide_base));
         // the key's comb and the context it was built for live in a buffer of the calling thread that outlives the call
         // (ThreadState::keep): the next call with the same context bytes finds them there.  The verdict on THIS call's context
-        // (wide_ok) is the call's own: a report word of its work slab (word 0 is the fast verification's slow-list count, word 1 the
-        // indexed X25519 call's ladder count), ordered between streams like the slab itself.
+        // (wide_ok) is the call's own: a report word of its work slab (capi_common.hpp: ReportWord), ordered between streams like the
+        // slab itself.
         void* keep = nullptr;
         bool fresh = false;
         constexpr size_t KEEP_WORDS = WB_TBL_WORDS + 16 * 32 + KEEP_CTX_WORDS + 1 + 3;
@@ -453,11 +457,8 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
         u32* wide_key = (u32*)keep;
         u32* check_rows = wide_key + WB_TBL_WORDS;
         u32* remembered = check_rows + 16 * 32;
-        unsigned* report = nullptr;
-        C25519_RC(tls().report_word_for(&report, stream));
-        wide_ok = report + 2;
-        tl_last_check.wide_ok = wide_ok; tl_last_check.stream = stream; tl_last_check.generation = tls().generation;
-        (void)hipGetDevice(&tl_last_check.device);
+        C25519_RC(tls().report_word_for(&wide_ok, c25519_host::REPORT_WIDE_OK, stream));
+        tl_last_check.reports_in(wide_ok, stream);
         k_ed25519_verify_ctx_prepare<<<build ? 1 + WB_NT * WB_ROWS / 128 : 1, 128, 0, stream>>>(wide_key, check_rows, wide_ok, (const u32*)ctx, remembered, build ? 1 : 0);
         C25519_TRY(hipGetLastError());
         if (build) {
@@ -476,9 +477,8 @@ static int verify_check_one_dev(void* verdict, const void* ctx, const void* sig,
     k_ed25519_verify_check_shared<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(
         scr, sig, (const u32*)ctx, msgs, n, tbl, wide_ok);
     C25519_TRY(hipGetLastError());
-    if (zip215) {                                           // rule 2 for the one context: word 1 behind the projective part
-        u32* key_ok = (u32*)w + proj_words(n) + 1;
-        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctx, 1, nullptr, key_ok, sig, (int*)verdict, stream));
+    if (zip215) {
+        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctx, 1, nullptr, cs.key_words + 1, sig, (int*)verdict, stream));
     } else {
         // (the quad kernel has written the verdicts itself where the combs decided: the shared inversion then finds wide_ok set and leaves)
         C25519_RC(launch_invert(scr, n, FinishVerify{ scr.a, scr.b, sig, (int*)verdict, n, quads ? wide_ok : nullptr }, stream));
@@ -533,12 +533,16 @@ static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ct
         C25519_TRY(hipGetLastError());
         return 0;
     }
-    const size_t row_words = C25519_INDEXED_REPACK ? n_ctx * QTABLE_CANON_WORDS : 0;
-    void* w = nullptr;
+    struct IndexedScratch { u32* rows; ProjScratch scr; u32* key_ok; } is;
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, (row_words + proj_words(n) + (zip215 ? round_up(n_ctx, 4) : 0)) * sizeof(u32), stream));
-    u32* rows = (u32*)w;                                    // first in the slab (hipMalloc: 256-byte aligned): whole 128-byte rows
-    const ProjScratch scr = carve_proj(rows + row_words, n);
+    C25519_RC(lease_scratch(&is, lease, stream, [=](Carve& c) {
+        IndexedScratch s;
+        s.rows = c.take(C25519_INDEXED_REPACK ? n_ctx * QTABLE_CANON_WORDS : 0);   // first in the slab (hipMalloc: 256-byte aligned): whole 128-byte rows
+        s.scr = c.proj(n);
+        s.key_ok = c.take4(zip215 ? n_ctx : 0);              // rule 2 per context (ZIP-215)
+        return s;
+    }));
+    const auto& [rows, scr, key_ok] = is;
 #if C25519_INDEXED_REPACK
     k_ed25519_verify_ctx_repack<<<grid_for(n_ctx * (QTABLE_CANON_WORDS / 4), 256), 256, 0, stream>>>((uint4*)rows, (const u32*)ctxs, n_ctx);
     C25519_TRY(hipGetLastError());
@@ -546,9 +550,8 @@ static int verify_check_indexed_dev(void* verdict, const void* ctxs, size_t n_ct
     k_ed25519_verify_check_indexed<<<grid_for(n, ED_BLOCK), ED_BLOCK, 0, stream>>>(scr, sig, (const u32*)ctxs, n_ctx, (const u32*)ctx_index,
                                                                                   msgs, n, tbl, rows);
     C25519_TRY(hipGetLastError());
-    if (zip215)                                             // rule 2 per context: n_ctx words behind the projective part
-        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, rows + row_words + proj_words(n), sig,
-                                      (int*)verdict, stream));
+    if (zip215)
+        C25519_RC(launch_coset_finish(scr, n, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, key_ok, sig, (int*)verdict, stream));
     else
         C25519_RC(launch_invert(scr, n, FinishVerifyIndexed{ scr.a, scr.b, sig, (int*)verdict, n, (const u32*)ctx_index, n_ctx }, stream));
     return lease.release();
@@ -579,9 +582,7 @@ int ed25519_Verify_Check_zip215_dev(void* verdict, const void* ctx, const void* 
     if (int rc = check_dev_args(n, { verdict, ctx, sig })) return rc;
     if (n == 0) return 0;
     if (!zip215_check_walks(n)) {
-        tl_last_check = LastCheck();
-        tl_last_check.ran = true;
-        tl_last_check.generation = tls().generation;
+        tl_last_check = c25519_host::LastCall::known(0);
         return zip215_check_gathered((int*)verdict, ctx, 1, nullptr, sig, fixed_msgs(msg, msg_size), n, (hipStream_t)stream_);
     }
     return verify_check_one_dev(verdict, ctx, sig, msg, msg_size, n, (hipStream_t)stream_, true);
@@ -610,15 +611,8 @@ int ed25519_Verify_Check_zip215_indexed_ragged_dev(void* verdict, const void* ct
 long c25519_amd_verify_check_last_wide(void)
 {
     C25519_API_CALL_OR(-1);
-    const LastCheck& lc = tl_last_check;
-    if (!lc.ran || lc.generation != tls().generation) return -1;    // (c25519_amd_thread_release() / a device switch since)
-    if (!lc.wide_ok) return 0;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != lc.device) return -1;
-    if (hipStreamSynchronize(lc.stream) != hipSuccess) return -1;
-    u32 v = 0;
-    if (hipMemcpy(&v, lc.wide_ok, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return v ? 1 : 0;
+    const long v = tl_last_check.read();
+    return v > 0 ? 1 : v;
 }
 
 }  // extern "C"

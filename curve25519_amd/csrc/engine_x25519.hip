@@ -507,7 +507,7 @@ int c25519_amd_probe_words(void) { return PROBE_WORDS; }
 
 // ---- device-pointer entry points ----------------------------------------------------------------
 
-// work: null, or scratch of at least proj_words(n) words the caller holds already (a lease of its own on this stream)
+// work: null, or the projective part's scratch (Carve::proj(n)) the caller holds already on this stream, in a lease of its own
 static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t stream, u32* work = nullptr)
 {
     if (x25519_quad_for(n)) {                                 // four lanes per element
@@ -529,16 +529,15 @@ static int x25519_dev(void* out, const void* pk, void* sk, size_t n, hipStream_t
         return 0;
     }
     if (x25519_split_for(n)) {
-        void* w = work;
+        ProjScratch scr;
         c25519_host::WorkLease lease;
-        if (!work) C25519_RC(lease.acquire(&w, proj_words(n) * sizeof(u32), stream));
-        const ProjScratch scr = carve_proj((u32*)w, n);
+        C25519_RC(lease_proj(&scr, lease, n, stream, work));
         note_shape(SHAPE_LANE_INVERT, XL_BLOCK);
         if (pk) k_x25519_ladder<false><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         else    k_x25519_ladder<true><<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr.a, scr.z, pk, sk, n);
         C25519_TRY(hipGetLastError());
         C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
-        return work ? 0 : lease.release();
+        return lease.release();
     }
     const int block = x25519_block_for(n);
     note_shape(SHAPE_LANE, block);
@@ -578,9 +577,8 @@ int curve25519_dh_CalculatePublicKey_dev(void* pk, void* sk, size_t n, void* str
 constexpr long ONE_PEER_WIDE_DEFAULT = 3L << 15;
 
 // what the calling thread's last one-peer call on this device left behind for c25519_amd_x25519_one_peer_last_wide: where its
-// "the comb decides this call" word lives (null: the call never asked the device)
-struct LastPeer { const u32* wide_ok = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; bool ran = false; };
-static thread_local LastPeer tl_last_peer;
+// 0 (the call never asked the device), or where its "the comb decides this call" word lives
+static thread_local c25519_host::LastCall tl_last_peer;
 
 // Above the per-wave range a thread that has kept a peer comb asks the device, at any size, whether this call's key is that peer
 // (one lane, 72 bytes); from ONE_PEER_WIDE elements on (the whole of a pipelined *_batch call counts) a new eligible peer gets
@@ -597,30 +595,31 @@ static int x25519_one_peer_dev(void* out, const void* pk, void* sk, size_t n, hi
     const bool per_wave = !quads && x25519_coop_for(n);
     const bool build = wide_from > 0 && whole >= (size_t)wide_from;
     const bool reuse = !build && wide_from > 0 && !per_wave && tls().has_keep(ThreadState::KEEP_PEER);
-    tl_last_peer = LastPeer();
-    tl_last_peer.ran = true;
-    tl_last_peer.generation = tls().generation;
+    tl_last_peer = c25519_host::LastCall::known(0);
     if (!build && !reuse && per_wave) {                      // a few elements: one (or two) waves per element, as x25519_dev runs them
-        void* w = nullptr;
         c25519_host::WorkLease lease;
         const void* keys = pk;
         if (n > 1) {
-            C25519_RC(lease.acquire(&w, 32 * n, stream));
-            k_x25519_peer_broadcast<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)w, (const uint4*)pk, n);
+            u32* copies = nullptr;                            // the key, n times
+            C25519_RC(lease_scratch(&copies, lease, stream, [n](Carve& c) { return c.take(8 * n); }));
+            k_x25519_peer_broadcast<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)copies, (const uint4*)pk, n);
             C25519_TRY(hipGetLastError());
-            keys = w;
+            keys = copies;
         }
         const CallWords cw{};                                 // (records from memory: pk is device memory even in a zero-copy call)
         if (x25519_two_waves_for(n)) k_x25519_coop2<<<(unsigned)n, 128, 0, stream>>>(out, keys, sk, n, take_done_word(n), cw);
         else k_x25519_coop<false><<<(unsigned)n, 64, 0, stream>>>(out, keys, sk, n, take_done_word(n), cw);
         C25519_TRY(hipGetLastError());
-        return n > 1 ? lease.release() : 0;
+        return lease.release();
     }
-    void* w = nullptr;
+    ProjScratch scr;
     c25519_host::WorkLease lease;
-    const bool scratch = build || reuse || !quads;           // (the quads' ladder writes its results itself)
-    C25519_RC(lease.acquire(&w, scratch ? proj_words(n) * sizeof(u32) : 256, stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
+    const bool scratch = build || reuse || !quads;           // (the quads' ladder writes its results itself: 256 bytes nobody uses)
+    C25519_RC(lease_scratch(&scr, lease, stream, [=](Carve& c) {
+        if (scratch) return c.proj(n);
+        c.take(64);
+        return ProjScratch{};
+    }));
     const u32* wide_ok = nullptr;
     c25519_host::KeepLease keep_lease;                        // records the kept buffer's event however this call leaves
     if (build || reuse) {
@@ -641,8 +640,7 @@ static int x25519_one_peer_dev(void* out, const void* pk, void* sk, size_t n, hi
         }
         k_x25519_one_peer_mult<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(scr, sk, n, wide_peer, flags);
         C25519_TRY(hipGetLastError());
-        tl_last_peer.wide_ok = wide_ok; tl_last_peer.stream = stream;
-        (void)hipGetDevice(&tl_last_peer.device);
+        tl_last_peer.reports_in(wide_ok, stream);
     }
     if (quads) {
         k_x25519_quad_one_peer<<<grid_for(n, quad::ELEMS_PER_WAVE), 64, 0, stream>>>(out, pk, sk, n, wide_ok);
@@ -673,15 +671,8 @@ int curve25519_dh_CreateSharedKey_one_peer_dev(void* shared, const void* pk, voi
 long c25519_amd_x25519_one_peer_last_wide(void)
 {
     C25519_API_CALL_OR(-1);
-    const LastPeer& lp = tl_last_peer;
-    if (!lp.ran || lp.generation != tls().generation) return -1;    // (c25519_amd_thread_release() / a device switch since)
-    if (!lp.wide_ok) return 0;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != lp.device) return -1;
-    if (hipStreamSynchronize(lp.stream) != hipSuccess) return -1;
-    u32 v = 0;
-    if (hipMemcpy(&v, lp.wide_ok, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return v ? 1 : 0;
+    const long v = tl_last_peer.read();
+    return v > 0 ? 1 : v;
 }
 
 // ---- many secrets, many peer contexts -------------------------------------------------------------------------
@@ -697,13 +688,13 @@ int curve25519_dh_Peer_Init_dev(void* ctx, const void* pk, size_t n, void* strea
     if (n == 0) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t chunk = std::min(n, PEER_INIT_CHUNK);
-    void* w = nullptr;
+    u32* w = nullptr;                                         // a launch's lane-private tables
     c25519_host::WorkLease lease;
-    C25519_RC(lease.acquire(&w, chunk * QTABLE_LIMB_WORDS * sizeof(u32), stream));
+    C25519_RC(lease_scratch(&w, lease, stream, [chunk](Carve& c) { return c.take(chunk * QTABLE_LIMB_WORDS); }));
     for (size_t lo = 0; lo < n; lo += chunk) {
         const size_t c = std::min(chunk, n - lo);
         k_x25519_peer_init<<<grid_for(c, ED_BLOCK), ED_BLOCK, 0, stream>>>((u32*)ctx + lo * PEER_CTX_WORDS, (const uint4*)pk + 2 * lo, c,
-                                                                             (u32*)w);
+                                                                             w);
         C25519_TRY(hipGetLastError());
     }
     return lease.release();
@@ -717,50 +708,54 @@ constexpr long PEER_INDEXED_MIN_DEFAULT = 2049;
 
 // what the calling thread's last indexed call on this device left behind for c25519_amd_x25519_indexed_last_ladder_elements: the
 // elements the host knows ran the ladder (the whole call below PEER_INDEXED_MIN), or the device word the ladder kernel reports in
-struct LastIndexed { long host = -1; const u32* report = nullptr; hipStream_t stream = nullptr; int device = -1; unsigned long generation = 0; };
-static thread_local LastIndexed tl_last_indexed;
+static thread_local c25519_host::LastCall tl_last_indexed;
 
 static int x25519_indexed_dev(void* out, const void* ctxs, size_t n_ctx, const void* ctx_index, void* sk, size_t n, hipStream_t stream)
 {
     const long min_walk = c25519_host::tunable_or(c25519_host::T_PEER_INDEXED_MIN, PEER_INDEXED_MIN_DEFAULT);
     const size_t whole = std::max(n, c25519_host::batch_shape_hint());
-    tl_last_indexed = LastIndexed();
-    void* w = nullptr;
+    tl_last_indexed = c25519_host::LastCall();
     c25519_host::WorkLease lease;
     if (whole < (size_t)std::max(min_walk, 0L)) {
-        const size_t key_words = round_up(8 * n, 4);
         const bool split = !x25519_quad_for(n) && !x25519_coop_for(n) && x25519_split_for(n);
-        C25519_RC(lease.acquire(&w, (key_words + (split ? proj_words(n) : 0)) * sizeof(u32), stream));
-        k_x25519_peer_gather<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)w, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
+        struct Gathered { u32 *keys, *work; } g;
+        C25519_RC(lease_scratch(&g, lease, stream, [=](Carve& c) {
+            Gathered s;
+            s.keys = c.take4(8 * n);
+            s.work = split ? c.proj(n).a : nullptr;          // x25519_dev's scratch where it runs ladder and inversion in two launches
+            return s;
+        }));
+        k_x25519_peer_gather<<<grid_for(2 * n, 256), 256, 0, stream>>>((uint4*)g.keys, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n);
         C25519_TRY(hipGetLastError());
         bool& zero_copy = c25519_host::zero_copy_call();      // the gathered keys are device memory, not the call's host records
         const bool zc = zero_copy;
         zero_copy = false;
-        const int rc = x25519_dev(out, w, sk, n, stream, split ? (u32*)w + key_words : nullptr);
+        const int rc = x25519_dev(out, g.keys, sk, n, stream, g.work);
         zero_copy = zc;
         C25519_RC(rc);
-        tl_last_indexed.host = (long)n;
-        tl_last_indexed.generation = tls().generation;
+        tl_last_indexed = c25519_host::LastCall::known((long)n);
         return lease.release();
     }
     unsigned* report = nullptr;
-    C25519_RC(tls().report_word_for(&report, stream));
-    C25519_RC(lease.acquire(&w, (proj_words(n) + round_up(n, 4) + 4) * sizeof(u32), stream));
-    const ProjScratch scr = carve_proj((u32*)w, n);
-    u32* list = (u32*)w + proj_words(n);
-    u32* count = list + round_up(n, 4);
+    C25519_RC(tls().report_word_for(&report, c25519_host::REPORT_LADDER_ELEMENTS, stream));
+    struct WalkScratch { ProjScratch scr; u32 *list, *count; } ws;
+    C25519_RC(lease_scratch(&ws, lease, stream, [n](Carve& c) {
+        WalkScratch s;
+        s.scr = c.proj(n);
+        s.list = c.take4(n);                                 // the elements the ladder has to run ...
+        s.count = c.take(4);                                 // ... and how many: one word used
+        return s;
+    }));
+    const auto& [scr, list, count] = ws;
     C25519_TRY(hipMemsetAsync(count, 0, sizeof(u32), stream));
     k_x25519_peer_indexed_walk<<<grid_for(n, WB_BLOCK), WB_BLOCK, 0, stream>>>(scr, sk, (const u32*)ctxs, n_ctx, (const u32*)ctx_index, n,
                                                                               list, count);
     C25519_TRY(hipGetLastError());
     k_x25519_peer_indexed_ladder<<<grid_for(n, XL_BLOCK), XL_BLOCK, 0, stream>>>(scr, sk, (const u32*)ctxs, (const u32*)ctx_index, n,
-                                                                                list, count, report + 1);
+                                                                                list, count, report);
     C25519_TRY(hipGetLastError());
     C25519_RC(launch_invert(scr, n, FinishX25519{ scr.a, out, n }, stream));
-    tl_last_indexed.report = report + 1;                      // (word 0 is the fast verification's slow-list report)
-    tl_last_indexed.stream = stream;
-    tl_last_indexed.generation = tls().generation;
-    (void)hipGetDevice(&tl_last_indexed.device);
+    tl_last_indexed.reports_in(report, stream);
     return lease.release();
 }
 
@@ -781,16 +776,7 @@ int curve25519_dh_CreateSharedKey_indexed_dev(void* shared, const void* ctxs, si
 long c25519_amd_x25519_indexed_last_ladder_elements(void)
 {
     C25519_API_CALL_OR(-1);
-    const LastIndexed& li = tl_last_indexed;
-    if (li.generation != tls().generation) return -1;        // (c25519_amd_thread_release() / a device switch since)
-    if (li.host >= 0) return li.host;
-    if (!li.report) return -1;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != li.device) return -1;
-    if (hipStreamSynchronize(li.stream) != hipSuccess) return -1;
-    u32 v = 0;
-    if (hipMemcpy(&v, li.report, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (long)v;
+    return tl_last_indexed.read();
 }
 
 }  // extern "C"

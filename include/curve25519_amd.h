@@ -751,8 +751,12 @@ long c25519_amd_verify_check_last_wide(void);
  * -1: no such call yet, or c25519_amd_thread_release() since.  Does not synchronise: the value is the host's. */
 long c25519_amd_last_shape(void);
 
-/* bytes of device scratch ed25519_VerifySignature_dev needs for n elements (per-lane 4-fold tables);
- * the library allocates and caches it per host thread (about 2.8 KB per element). */
+/* bytes of device scratch ed25519_VerifySignature_dev needs for n elements; the library allocates and caches it per host thread
+ * (about 2.8 KB per element; r4 = rounded up to 4):
+ *   4 * (n * 640 + 4 * r4(10 n) + r4(14 n) + 2 * r4(5 n) + 5 * r4(n) + 4)
+ * -- per element the per-lane tables (640 words: the reference order's 4-fold table, the larger of the two paths' formats), the
+ * projective result with its prefix products (4 x 10 words), the lattice path's scalars (14 + 5 + 5 words), its flag, slow-list and
+ * order words and two point flags; four counter words per call. */
 size_t ed25519_VerifySignature_scratch_bytes(size_t n);
 
 /* Two-phase verification (reference include/ed25519_signature.h:77-93): one key, many signatures.
