@@ -255,7 +255,7 @@ struct KeptRecord {
 struct GrowArray {
     void* dev = nullptr;
     size_t cap = 0;
-    int upload(void** out, const void* src, size_t bytes)
+    int reserve(void** out, size_t bytes)                  // at least `bytes`, content undefined
     {
         if (bytes > cap) {
             if (dev) { C25519_RC(zero_device_now(dev, cap)); C25519_TRY(hipFree(dev)); }
@@ -263,9 +263,13 @@ struct GrowArray {
             C25519_TRY(hipMalloc(&dev, bytes));
             cap = bytes;
         }
-        C25519_RC(upload_now(dev, src, bytes));
         *out = dev;
         return 0;
+    }
+    int upload(void** out, const void* src, size_t bytes)
+    {
+        C25519_RC(reserve(out, bytes));
+        return upload_now(dev, src, bytes);
     }
     void release()
     {
@@ -307,6 +311,7 @@ struct ThreadState {
     KeptRecord<192> bctx;
     KeptRecord<32> peer;
     GrowArray vctxs, pctxs, sctxs, bkeys;
+    GrowArray okey, ostage;                // the OPRF calls' server key, and the whole staging of a proof call (both zeroed before the call returns)
     void* hbuf[SETS][SLOTS] = {};          // pinned host staging (hipHostMalloc)
     size_t hcap[SETS][SLOTS] = {};
     // The completion word of a call of ONE element (host_pipeline.hpp: zero-copy calls): pinned host memory the call's last
@@ -527,6 +532,7 @@ struct ThreadState {
         done_offered = done_taken = false;
         vctx.release(); bctx.release(); peer.release();
         vctxs.release(); pctxs.release(); sctxs.release(); bkeys.release();
+        okey.release(); ostage.release();
         for (int l = 0; l < LANES; l++) {
             free_slab(lane_work[l]);
             if (stream[l]) (void)hipStreamDestroy(stream[l]);

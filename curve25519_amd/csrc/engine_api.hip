@@ -840,6 +840,135 @@ int ed25519_VRF_ProofToHash_batch(unsigned char* beta, int* ok, const unsigned c
     return row_call(n, { Out(beta, 64), Out(ok, sizeof(int)), In(proof, 80) }, ed25519_VRF_ProofToHash_dev);
 }
 
+// OPRF and VOPRF (engine_oprf.hip; csrc/oprf25519.cuh): the inputs are staged like a signing call's messages
+int ristretto255_OPRF_Blind_batch(unsigned char* blinded, int* ok, const unsigned char* input, size_t input_size, const unsigned char* blind, int mode,
+                                  size_t n)
+{
+    if (mode != 0 && mode != 1) return bad_arg("mode must be 0 (OPRF) or 1 (VOPRF)");
+    if (input_size > 65535) return bad_arg("input_size must be at most 65535");
+    return row_call(n, { Out(blinded, 32), Out(ok, sizeof(int)), In(input, input_size), In(blind, 32) },
+                    [=](void* b, void* o, void* in, void* bl, size_t c, hipStream_t st) -> int {
+                        return ristretto255_OPRF_Blind_dev(b, o, in, input_size, bl, mode, c, st);
+                    });
+}
+
+int ristretto255_OPRF_Finalize_batch(unsigned char* output, int* ok, const unsigned char* input, size_t input_size, const unsigned char* blind,
+                                     const unsigned char* evaluated, size_t n)
+{
+    if (input_size > 65535) return bad_arg("input_size must be at most 65535");
+    return row_call(n, { Out(output, 64), Out(ok, sizeof(int)), In(input, input_size), In(blind, 32), In(evaluated, 32) },
+                    [=](void* out, void* o, void* in, void* bl, void* ev, size_t c, hipStream_t st) -> int {
+                        return ristretto255_OPRF_Finalize_dev(out, o, in, input_size, bl, ev, c, st);
+                    });
+}
+
+// the ONE key has a device buffer of its own per calling thread, uploaded once per call and zeroed when the call returns
+int ristretto255_OPRF_BlindEvaluate_batch(unsigned char* evaluated, int* ok, const unsigned char* skS, const unsigned char* blinded, size_t n)
+{
+    C25519_API_CALL();
+    if (!evaluated || !ok || !skS || !blinded) return bad_arg("null pointer");
+    if (n == 0) return 0;
+    ThreadState& t = tls();
+    C25519_RC(t.ensure());
+    void* dsk = nullptr;
+    C25519_RC(t.okey.upload(&dsk, skS, 32));
+    const int rc = row_call(n, { Out(evaluated, 32), Out(ok, sizeof(int)), In(blinded, 32) },
+                            [=](void* ev, void* o, void* bl, size_t c, hipStream_t st) -> int {
+                                return ristretto255_OPRF_BlindEvaluate_dev(ev, o, dsk, bl, c, st);
+                            });
+    const std::string text = c25519_host::last_error();
+    const int wiped = c25519_host::zero_device_now(dsk, 32);
+    if (rc) c25519_host::last_error() = text;
+    return rc ? rc : wiped;
+}
+
+}  // extern "C"
+
+// The proof calls run as ONE piece on ONE stream: every array is uploaded whole into one staging buffer of the calling thread (cut
+// by the carver the scratch layouts use), `launch` gets the device pointers in list order, the outputs come back, the whole buffer
+// is zeroed -- it held skS and proof_rand -- and the call returns when the stream has drained.
+struct OprfStaged { const void* in; void* out; size_t bytes; };
+template <size_t K, typename Launch>
+static int oprf_one_piece(const OprfStaged (&arr)[K], Launch launch)
+{
+    ThreadState& t = tls();
+    C25519_RC(t.ensure());
+    hipStream_t st = t.stream[ThreadState::LANES - 1];       // the download stream, idle between pipelined calls
+    Carve size;
+    for (const OprfStaged& a : arr) size.take4((a.bytes + 3) / 4);
+    void* base = nullptr;
+    C25519_RC(t.ostage.reserve(&base, size.bytes() ? size.bytes() : 16));
+    Carve cut(base);
+    void* d[K];
+    for (size_t i = 0; i < K; i++) d[i] = cut.take4((arr[i].bytes + 3) / 4);
+    auto enqueue = [&]() -> int {
+        for (size_t i = 0; i < K; i++)
+            if (arr[i].in && arr[i].bytes) C25519_TRY(hipMemcpyAsync(d[i], arr[i].in, arr[i].bytes, hipMemcpyHostToDevice, st));
+        C25519_RC(launch(d, st));
+        for (size_t i = 0; i < K; i++)
+            if (arr[i].out && arr[i].bytes) C25519_TRY(hipMemcpyAsync(arr[i].out, d[i], arr[i].bytes, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    const int rc = enqueue();
+    const std::string text = c25519_host::last_error();
+    // whatever enqueue() said: the buffer is zeroed behind what was enqueued and the stream drained (it may still be reading the
+    // caller's arrays); the first failure is the call's
+    const hipError_t wiped = size.bytes() ? hipMemsetAsync(base, 0, size.bytes(), st) : hipSuccess;
+    const hipError_t drained = hipStreamSynchronize(st);
+    if (rc) {
+        (void)hipGetLastError();
+        c25519_host::last_error() = text;
+        return rc;
+    }
+    C25519_TRY(wiped);
+    C25519_TRY(drained);
+    return 0;
+}
+
+// offsets of a host-pointer proof call: from 0 to n in requests of 1 .. 65535 rows
+static int oprf_check_offsets(const uint64_t* offsets, size_t m, size_t n)
+{
+    if (offsets[0] != 0 || offsets[m] != n) return bad_arg("offsets must begin at 0 and end at n");
+    for (size_t j = 0; j < m; j++) {
+        if (offsets[j + 1] < offsets[j]) return bad_arg("offsets must not decrease");
+        if (offsets[j + 1] == offsets[j] || offsets[j + 1] - offsets[j] > 65535) return bad_arg("a request has 1 .. 65535 rows");
+    }
+    return 0;
+}
+
+extern "C" {
+
+int ristretto255_VOPRF_BlindEvaluate_batch(unsigned char* evaluated, unsigned char* proof, int* ok, int* req_ok, const unsigned char* skS,
+                                           const unsigned char* proof_rand, const unsigned char* blinded, const uint64_t* offsets, size_t m, size_t n)
+{
+    C25519_API_CALL();
+    if (!skS || !offsets || (n && (!evaluated || !ok || !blinded)) || (m && (!proof || !req_ok || !proof_rand))) return bad_arg("null pointer");
+    if (m > ((size_t)1 << 31) || n > ((size_t)1 << 31)) return bad_arg("batch too large (more than 2^31 requests or rows)");
+    if (int rc = oprf_check_offsets(offsets, m, n)) return rc;
+    if (n == 0 && m == 0) return 0;
+    const OprfStaged arr[] = { { nullptr, evaluated, 32 * n }, { nullptr, proof, 64 * m }, { nullptr, ok, sizeof(int) * n }, { nullptr, req_ok, sizeof(int) * m },
+                               { skS, nullptr, 32 }, { proof_rand, nullptr, 32 * m }, { blinded, nullptr, 32 * n }, { offsets, nullptr, sizeof(uint64_t) * (m + 1) } };
+    return oprf_one_piece(arr, [&](void** d, hipStream_t st) -> int {
+        return ristretto255_VOPRF_BlindEvaluate_dev(n ? d[0] : nullptr, m ? d[1] : nullptr, n ? d[2] : nullptr, m ? d[3] : nullptr, d[4], m ? d[5] : nullptr,
+                                                    n ? d[6] : nullptr, d[7], m, n, st);
+    });
+}
+
+int ristretto255_VOPRF_VerifyProof_batch(int* req_ok, const unsigned char* pkS, const unsigned char* blinded, const unsigned char* evaluated,
+                                         const unsigned char* proof, const uint64_t* offsets, size_t m, size_t n)
+{
+    C25519_API_CALL();
+    if (!pkS || !offsets || (n && (!blinded || !evaluated)) || (m && (!req_ok || !proof))) return bad_arg("null pointer");
+    if (m > ((size_t)1 << 31) || n > ((size_t)1 << 31)) return bad_arg("batch too large (more than 2^31 requests or rows)");
+    if (int rc = oprf_check_offsets(offsets, m, n)) return rc;
+    if (m == 0) return 0;
+    const OprfStaged arr[] = { { nullptr, req_ok, sizeof(int) * m }, { pkS, nullptr, 32 }, { blinded, nullptr, 32 * n }, { evaluated, nullptr, 32 * n },
+                               { proof, nullptr, 64 * m }, { offsets, nullptr, sizeof(uint64_t) * (m + 1) } };
+    return oprf_one_piece(arr, [&](void** d, hipStream_t st) -> int {
+        return ristretto255_VOPRF_VerifyProof_dev(d[0], d[1], n ? d[2] : nullptr, n ? d[3] : nullptr, d[4], d[5], m, n, st);
+    });
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

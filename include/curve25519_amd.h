@@ -534,6 +534,112 @@ int ed25519_VRF_Verify_dev(void *beta, void *ok, const void *pk, const void *pro
 int ed25519_VRF_ProofToHash_batch(unsigned char *beta /* n x 64 */, int *ok, const unsigned char *proof, size_t n);
 int ed25519_VRF_ProofToHash_dev(void *beta, void *ok, const void *proof, size_t n, void *stream);
 
+/* An oblivious pseudorandom function: RFC 9497's OPRF (mode 0x00) and VOPRF (mode 0x01) with ciphersuite ristretto255-SHA512, the
+ * protocol the ristretto255, scalar and hashing calls above were built towards -- PSI and password hardening evaluate mode 0x00,
+ * Privacy Pass issuance and any auditable server mode 0x01 with its DLEQ proof over a batch of evaluations.  contextString is
+ * "OPRFV1-" || mode || "-ristretto255-SHA512"; lp(x) is I2OSP(len(x), 2) || x.  A 32-byte scalar (blind, skS, proof_rand) is read as
+ * a 256-bit little-endian integer mod L.  Elements are ristretto255 encodings; the identity is 32 zero bytes.
+ *   ristretto255_OPRF_Blind_* (3.3.1 / 3.3.2 Blind): blinded[i] = blind[i] * HashToGroup(input[i]) under the DST "HashToGroup-" ||
+ *     contextString of `mode`, which is 0 or 1 (anything else is an argument error).  All inputs of a call share one input_size, at
+ *     most 65535 (more is an argument error); 0 is allowed and input may then be NULL.  ok[i] = 0 where the result is the identity
+ *     (the RFC's InvalidInputError; blind[i] = 0 mod L gives it), and blinded[i] is then zero bytes anyway.  The caller supplies the
+ *     blinds: uniform, secret, one per input.
+ *   ristretto255_OPRF_Finalize_* (3.3.1 Finalize; 3.3.2 Finalize behind ristretto255_VOPRF_VerifyProof): output[i] = SHA-512(lp(input[i])
+ *     || lp(N) || "Finalize") with N = (1 / blind[i]) * evaluated[i]; the same for both modes.  ok[i] = 0 and 64 zero bytes where
+ *     evaluated[i] does not decode or is the identity, or where blind[i] = 0 mod L.
+ *   ristretto255_OPRF_BlindEvaluate_* (3.3.1 BlindEvaluate): evaluated[i] = skS * blinded[i] under ONE key for all rows, 32 bytes
+ *     (device memory in the *_dev form).  ok[i] = 0 and zero bytes where blinded[i] does not decode, or where it or the result is the
+ *     identity (skS = 0 mod L gives that for every row).
+ *   ristretto255_VOPRF_BlindEvaluate_* (3.3.2 BlindEvaluate, 2.2.1 GenerateProof with ComputeCompositesFast): m requests over n rows;
+ *     request j owns rows offsets[j] .. offsets[j+1] - 1, between 1 and 65535 of them (the RFC encodes a row's index in its proof as
+ *     I2OSP(i, 2)).  offsets has m + 1 uint64 entries: host memory in the *_batch form, where offsets[0] == 0, offsets[m] == n and
+ *     1 <= offsets[j+1] - offsets[j] <= 65535 are checked as argument errors; device memory in the *_dev form, where no entry is trusted (below).
+ *     evaluated[i] and ok[i] are as in ristretto255_OPRF_BlindEvaluate.  proof[j] = c || s, 64 bytes: with pkS = skS * B,
+ *     seed = SHA-512(lp(pkS) || lp("Seed-" || contextString)), d_i = HashToScalar(lp(seed) || I2OSP(i, 2) || lp(blinded_i) ||
+ *     lp(evaluated_i) || "Composite") for the request's i-th row, M = sum d_i * blinded_i, Z = skS * M, r = proof_rand[j], t2 = r * B,
+ *     t3 = r * M: c = HashToScalar(lp(pkS) || lp(M) || lp(Z) || lp(t2) || lp(t3) || "Challenge"), s = r - c * skS mod L.  HashToScalar
+ *     is ed25519_HashToScalar under "HashToScalar-" || contextString.  proof_rand is the RFC's random scalar r, supplied by the
+ *     caller: it MUST be uniform, secret and used for one proof only (two proofs under one r give skS away).  req_ok[j] = 0 and
+ *     a zero proof where a row of the request has ok = 0; where the request is empty, longer than 65535 or not inside [0, n]; where
+ *     proof_rand[j] = 0 mod L (s would be -c * skS: the bytes of 0 and of L are both refused); where skS = 0 mod L.  Other
+ *     requests are not affected.  A row that no well-formed request owns gets ok = 0 and zero bytes.
+ *   ristretto255_VOPRF_VerifyProof_* (2.2.2 VerifyProof with ComputeComposites): req_ok[j] = 1 exactly when the request is well formed,
+ *     every one of its rows of blinded and evaluated decodes and is not the identity, c and s of proof[j] are below L, pkS decodes and
+ *     is not the identity, and with M = sum d_i * blinded_i, Z = sum d_i * evaluated_i, t2 = s * B + c * pkS, t3 = s * M + c * Z the
+ *     recomputed challenge equals c.
+ *   ristretto255_VOPRF_scratch_bytes(m, n): the device scratch the larger of the two proof calls leases for m requests over n rows,
+ *     4 * (8 * r4(10 n) + 2 * r4(n) + 32) bytes (r4: rounded up to a multiple of 4): an extended point or two a row, the request that owns
+ *     each row, pkS and the seed.
+ *   Differences from the RFC's one-request API: ok is per row and req_ok per request instead of an error for the call; the random
+ *     scalars are the caller's; one key per call; one proof covers at most 65535 rows.  Left out: POPRF (mode 0x02), many server
+ *     keys in one call, cutting one proof's rows across pipeline pieces, and a bucket-method multi-scalar multiplication for the
+ *     composites (a proof's 65535 rows are below the measured crossover of the batch equation's).
+ *   Malformed offsets in the *_dev forms: the request that owns a row is found by a bisection over offsets, which ends after at most
+ *     32 steps and reads entries 0 .. m only whatever they hold; a request counts as well formed when offsets[j] < offsets[j+1],
+ *     their difference is at most 65535 and offsets[j+1] <= n, and its proof is made or accepted only when the bisection gave every
+ *     one of its rows to it.  Anything else is req_ok = 0 (and ok = 0 for the rows nobody owns), never an access outside the arrays.
+ *   Inputs are never written.  Every row of every output is written; a refused call writes nothing.  n == 0 (and m == 0) returns 0,
+ *   with or without a device; a null pointer is an argument error.  Without a device every other call fails with an error code and
+ *   text: there is no CPU result.  *_dev forms never synchronise and take 16-byte aligned device pointers.  The three per-row
+ *   *_batch forms stage through the calling thread's pipeline in pieces like their neighbours (skS is uploaded once per call); the
+ *   two proof calls run as ONE piece: upload, the *_dev call, download.  The device copy of skS (the per-row form's and the proof
+ *   calls') and the proof calls' whole staging, proof_rand included, are zeroed before the call returns.  input and blind of the
+ *   Blind and Finalize *_batch forms travel through the pipeline's staging buffers like signing keys: those are zeroed when they are
+ *   replaced or released (c25519_amd_thread_release), not per call.
+ *   c25519_amd_last_shape is not written.
+ *   Secrecy.  input, blind, skS, proof_rand and what is derived from them before it is published are secret; blinded, evaluated,
+ *     pkS, d_i, M, Z, c and s are public.  No branch condition and no load or store address derives from a secret, with the one
+ *     exception of the base comb's row fetch for skS * B and r * B in the VOPRF server, exactly as in signing.  skS and proof_rand
+ *     are read from device memory where they are used and are never kernel arguments, and no secret is written to device memory:
+ *     the server's scratch holds d_i * blinded_i, the request that owns each row, pkS and the seed.
+ * The per-row calls are ONE kernel each, one lane per row, no scratch (csrc/oprf25519.cuh, csrc/engine_oprf.hip): Blind hands the sum
+ * of the two Elligator maps to the walk as it stands, without ENCODE and DECODE in between; Finalize inverts mod L and hashes in the
+ * lane.  The proof calls are three kernels on the caller's stream over one lease of scratch -- one lane for pkS and the seed, one
+ * lane per row (the server: D_i = skS * C_i and d_i * C_i over ONE window table of C_i), one lane per request (the sum of its rows'
+ * points, the walks, four encodings, the challenge) -- and allocate nothing else, so a call can be captured into a graph.  A
+ * request's rows are summed by ONE lane: a call of many small requests fills the device, one proof over tens of thousands of rows
+ * waits for that lane.
+ * Every kernel is without scratch memory; the per-row kernels and both row stages run at two waves per SIMD (the server's row lane
+ * builds C_i's two table rows a second time rather than keep them under the encoding of D_i; the verifier's rows take a lane per
+ * point), the per-request stages at one.
+ * Measured (tools/oprf_rate.py, profiles/oprf_rate.txt; interleaved rounds, inputs of 32 bytes, beside each call on the same inputs
+ * in the same process the composed sequence of existing *_dev calls a caller had before, without its host hashes): at 2^20 rows
+ * Blind_dev takes 13.73 ms (76.4 M/s; spread of the rounds 0.19 ms) against 14.95 ms for HashToGroup_dev + ScalarMult_dev, 0.92 x;
+ * Finalize_dev 12.76 ms (82.2 M/s), 1.03 x ScalarInvert_dev + ScalarMult_dev (12.42 ms), which leaves the hashes to the host: SLOWER
+ * than that sequence by 0.33 ms, its hash's price, where the sequence with the download and a per-item host SHA-512 loop behind it
+ * took 626 ms; OPRF_BlindEvaluate_dev 12.24 ms (85.7 M/s), 0.99 x ScalarMult_dev with the key repeated 2^20 times (12.31 ms).
+ * VOPRF_BlindEvaluate_dev over requests of 64 rows 26.23 ms (40.0 M rows/s), 0.97 x its composed sequence (two ScalarMult_dev and a
+ * HashToScalar_dev per row, the per-request calls; WITHOUT the sums, which no existing call does: 27.12 ms), 2.14 x one ScalarMult_dev;
+ * VOPRF_VerifyProof_dev 28.19 ms (37.2 M rows/s), 0.97 x composed.  By request size at 2^20 rows, server / verifier: requests of 1
+ * row 53.7 / 67.2 ms, of 64 rows 27.1 / 28.4 ms, of 4096 rows 48.5 / 68.5 ms, of 65535 rows 249 / 600 ms -- ONE lane sums a
+ * request's rows, so few large requests wait for that lane; issuance-sized requests are the case the calls are built for.  Up to
+ * 2^16 rows a call is one lane's latency: 0.97-1.15 ms (Blind; composed 1.08-1.26), 0.91-1.04 (Finalize), 0.87-0.97
+ * (OPRF_BlindEvaluate), 3.9-4.9 ms for the proof calls' three stages. */
+#define ristretto255_oprf_output_size 64
+#define ristretto255_voprf_proof_size 64
+#define ristretto255_voprf_max_rows   65535
+int ristretto255_OPRF_Blind_batch(unsigned char *blinded /* n x 32 */, int *ok, const unsigned char *input, size_t input_size,
+                                  const unsigned char *blind /* n x 32 */, int mode, size_t n);
+int ristretto255_OPRF_Blind_dev(void *blinded, void *ok, const void *input, size_t input_size, const void *blind, int mode, size_t n, void *stream);
+int ristretto255_OPRF_Finalize_batch(unsigned char *output /* n x 64 */, int *ok, const unsigned char *input, size_t input_size,
+                                     const unsigned char *blind, const unsigned char *evaluated, size_t n);
+int ristretto255_OPRF_Finalize_dev(void *output, void *ok, const void *input, size_t input_size, const void *blind, const void *evaluated, size_t n,
+                                   void *stream);
+int ristretto255_OPRF_BlindEvaluate_batch(unsigned char *evaluated /* n x 32 */, int *ok, const unsigned char *skS /* 32 */,
+                                          const unsigned char *blinded, size_t n);
+int ristretto255_OPRF_BlindEvaluate_dev(void *evaluated, void *ok, const void *skS, const void *blinded, size_t n, void *stream);
+int ristretto255_VOPRF_BlindEvaluate_batch(unsigned char *evaluated /* n x 32 */, unsigned char *proof /* m x 64 */, int *ok /* n */, int *req_ok /* m */,
+                                           const unsigned char *skS /* 32 */, const unsigned char *proof_rand /* m x 32 */,
+                                           const unsigned char *blinded /* n x 32 */, const uint64_t *offsets /* m + 1 */, size_t m, size_t n);
+int ristretto255_VOPRF_BlindEvaluate_dev(void *evaluated, void *proof, void *ok, void *req_ok, const void *skS, const void *proof_rand,
+                                         const void *blinded, const void *offsets, size_t m, size_t n, void *stream);
+int ristretto255_VOPRF_VerifyProof_batch(int *req_ok /* m */, const unsigned char *pkS /* 32 */, const unsigned char *blinded /* n x 32 */,
+                                         const unsigned char *evaluated /* n x 32 */, const unsigned char *proof /* m x 64 */,
+                                         const uint64_t *offsets /* m + 1 */, size_t m, size_t n);
+int ristretto255_VOPRF_VerifyProof_dev(void *req_ok, const void *pkS, const void *blinded, const void *evaluated, const void *proof,
+                                       const void *offsets, size_t m, size_t n, void *stream);
+size_t ristretto255_VOPRF_scratch_bytes(size_t m, size_t n);
+
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
  * element through the reference's own operation order in a kernel behind the walk.  Measured at n = 2^20
