@@ -60,6 +60,10 @@ _PAIRS = {
     "ristretto255_OPRF_BlindEvaluate": [_vp, _vp, _vp, _vp, _sz],
     "ristretto255_VOPRF_BlindEvaluate": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz],
     "ristretto255_VOPRF_VerifyProof": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_MultiScalarMult": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ed25519_MultiScalarMult_vartime": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ristretto255_MultiScalarMult": [_vp, _vp, _vp, _vp, _sz, _sz],
+    "ristretto255_MultiScalarMult_vartime": [_vp, _vp, _vp, _vp, _sz, _sz],
     "ed25519_VerifySignature_ragged": [_vp, _vp, _vp, _vp, _vp, _sz],
     "ed25519_VerifySignature": [_vp, _vp, _vp, _vp, _sz, _sz],
     "ed25519_VerifySignature_strict": [_vp, _vp, _vp, _vp, _sz, _sz],
@@ -97,6 +101,7 @@ SIGNATURES = {
     "c25519_amd_verify_batch_indexed_point_dev": [_vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "ed25519_VerifySignature_scratch_bytes": [_sz],
     "ristretto255_VOPRF_scratch_bytes": [_sz, _sz],
+    "c25519_MultiScalarMult_scratch_bytes": [_sz, _sz, C.c_int],
     "c25519_amd_verify_last_slow_elements": [],
     "c25519_amd_verify_check_last_wide": [],
     "c25519_amd_last_shape": [],
@@ -148,6 +153,7 @@ _RESTYPE = {
     "ed25519_VerifyBatch_scratch_bytes": _sz,
     "ed25519_VerifyBatch_indexed_scratch_bytes": _sz,
     "ristretto255_VOPRF_scratch_bytes": _sz,
+    "c25519_MultiScalarMult_scratch_bytes": _sz,
     "c25519_amd_verify_batch_last_equation": C.c_long,
     "c25519_amd_verify_last_slow_elements": C.c_long,
     "c25519_amd_verify_check_last_wide": C.c_long,

@@ -36,7 +36,7 @@ def is_stale() -> bool:
 
 
 ENGINE_UNITS = ("engine_x25519", "engine_fixed_base", "engine_verify", "engine_verify_ctx", "engine_keys", "engine_group",
-                "engine_ristretto", "engine_scalar", "engine_h2c", "engine_vrf", "engine_oprf", "engine_batch_eq", "engine_api")   # csrc/engine_common.cuh says which is which; csrc/engine.hip includes the same thirteen
+                "engine_ristretto", "engine_scalar", "engine_h2c", "engine_vrf", "engine_oprf", "engine_batch_eq", "engine_msm", "engine_api")   # csrc/engine_common.cuh says which is which; csrc/engine.hip includes the same fourteen
 OBJ = os.path.join(PKG, "_obj")             # git-ignored, does not travel: the GPU box gets the linked libraries
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-pragma-unroll-threshold=131072"]
 # -pragma-unroll-threshold: k_batch_invert keeps 16 elements and their prefix products in registers, which needs its

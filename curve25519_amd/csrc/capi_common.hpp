@@ -102,6 +102,8 @@ enum Tunable {
     T_ZIP215_CHECK_MIN,         // ed25519_Verify_Check_zip215*: smallest call that walks the contexts (0: always); below it the per-element call on the gathered keys
     T_SCALARMULT_WINDOW,        // ed25519_ScalarMult*: the window width of the variable-base walk, 2..4 (anything else: the built-in choice)
     T_SC_INVERT_K,              // ed25519_ScalarInvert: elements per inverting lane, 1, 2, 4, 8 or 16 (anything else: the built-in choice by n)
+    T_MSM_BUCKET_MIN,           // *_MultiScalarMult_vartime: smallest m that runs the bucket method (0: never; 1: always)
+    T_MSM_WINDOW,               // ... and its window width, 7..13 (anything else: the built-in choice by m)
     T_COUNT
 };
 constexpr long T_UNSET = -1;
@@ -110,7 +112,8 @@ inline const char* const* tunable_names()
     static const char* const names[T_COUNT] = { "COOP_MAX", "XF_SPLIT", "INV_K", "VERIFY_REFERENCE_ORDER", "MULTI_FORCE_GATHER",
                                                 "MULTI_VIRTUAL", "BASE_COMB", "HELPER_THREADS", "VERIFY_LAT_CAP_BITS", "ONE_KEY_WIDE", "LADDER2_MAX",
                                                 "QUAD_MIN", "QUAD_MAX", "ONE_PEER_WIDE", "PEER_INDEXED_MIN", "BATCH_EQ_MIN", "BATCH_EQ_WINDOW",
-                                                "BATCH_EQ_INDEXED_MIN", "ZIP215_CHECK_MIN", "SCALARMULT_WINDOW", "SC_INVERT_K" };
+                                                "BATCH_EQ_INDEXED_MIN", "ZIP215_CHECK_MIN", "SCALARMULT_WINDOW", "SC_INVERT_K", "MSM_BUCKET_MIN",
+                                                "MSM_WINDOW" };
     return names;
 }
 inline std::atomic<long>* tunable_table()

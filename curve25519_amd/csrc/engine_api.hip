@@ -969,6 +969,48 @@ int ristretto255_VOPRF_VerifyProof_batch(int* req_ok, const unsigned char* pkS, 
     });
 }
 
+}  // extern "C"
+
+// multiscalar multiplication (engine_msm.hip; csrc/msm_sum.cuh): ONE piece, like the proof calls -- a group is never cut across
+// pipeline pieces -- through their staging buffer, which is zeroed before the call returns (the plain calls' scalars are secret)
+typedef int (*msm_dev_fn)(void*, void*, const void*, const void*, size_t, size_t, void*);
+static int msm_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t m, size_t n_groups, msm_dev_fn call_dev)
+{
+    C25519_API_CALL();
+    if (!q || !ok || !scalar || !point) return bad_arg("null pointer");
+    if (m == 0) return bad_arg("m must be at least 1");
+    if (m > ((size_t)1 << 26)) return bad_arg("group too large for one call (m > 2^26)");
+    if (n_groups > ((size_t)1 << 31) / m) return bad_arg("batch too large (n_groups * m > 2^31)");
+    if (n_groups == 0) return 0;
+    const size_t rows = m * n_groups;
+    const OprfStaged arr[] = { { nullptr, q, 32 * n_groups }, { nullptr, ok, sizeof(int) * n_groups }, { scalar, nullptr, 32 * rows },
+                               { point, nullptr, 32 * rows } };
+    return oprf_one_piece(arr, [&](void** d, hipStream_t st) -> int { return call_dev(d[0], d[1], d[2], d[3], m, n_groups, st); });
+}
+
+extern "C" {
+
+int ed25519_MultiScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t m, size_t n_groups)
+{
+    return msm_batch(q, ok, scalar, point, m, n_groups, ed25519_MultiScalarMult_dev);
+}
+
+int ed25519_MultiScalarMult_vartime_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t m, size_t n_groups)
+{
+    return msm_batch(q, ok, scalar, point, m, n_groups, ed25519_MultiScalarMult_vartime_dev);
+}
+
+int ristretto255_MultiScalarMult_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t m, size_t n_groups)
+{
+    return msm_batch(q, ok, scalar, point, m, n_groups, ristretto255_MultiScalarMult_dev);
+}
+
+int ristretto255_MultiScalarMult_vartime_batch(unsigned char* q, int* ok, const unsigned char* scalar, const unsigned char* point, size_t m,
+                                               size_t n_groups)
+{
+    return msm_batch(q, ok, scalar, point, m, n_groups, ristretto255_MultiScalarMult_vartime_dev);
+}
+
 // signatures under many signer contexts (secret: the device copy is zeroed before it is freed or replaced)
 int ed25519_SignMessage_indexed_batch(unsigned char* sig, const void* ctxs, size_t n_ctx, const uint32_t* ctx_index,
                                       const unsigned char* msg, size_t msg_size, size_t n)

@@ -4,25 +4,12 @@
 // (one of the engine's translation units: engine_common.cuh says which is which; the lane-level code: msm25519.cuh)
 #include "engine_common.cuh"
 #include "msm25519.cuh"
+#include "msm_stages.cuh"
 
 #include <cerrno>
 #include <sys/random.h>
 
-// scratch of one equation, cut from the calling thread's slab (batcheq_layout): n elements, N = 2n points (keys, then R's),
-// K = (wa + 1) * buckets counters (the windows of buckets: msm25519.cuh, MsmShape)
-struct BatchEqScratch {
-    u32* rows;              // [N][32]  packed row of -P (msm_point_row), 128-byte aligned
-    u32* buckets;           // [K][40]  bucket sums
-    u32* windows;           // [wa + 1][40] window sums
-    u32* sc;                // [8][N]   biased scalars, word-major: a_i for key i, z_i for R i
-    u32* entries;           // [n (wa + wz)] the inverted index: point * 2 + sign, grouped by (window, bucket)
-    u32* partial;           // [blocks][16] per-workgroup sums of the s_i, in 16-bit chunks
-    u32* flags;             // [n]      non-zero: the element is left out (S >= L, a key or an R that does not decode)
-    u32* counts;            // [K]      entries per (window, bucket)
-    u32* cursor;            // [K]      where the bucket's list begins; after the scatter, where it ends
-    u32* reject;            // [1]      non-zero: some element was left out -> result 0
-};
-typedef MsmShape BatchEqShape;                               // (msm25519.cuh)
+// (BatchEqScratch, the scratch of one equation as the kernels take it, and BatchEqShape: msm_stages.cuh)
 struct BatchEqSeed { u32 w[8]; };
 
 constexpr int BE_BLOCK = 256;
@@ -654,6 +641,26 @@ int keyeq_dev(void* result, const void* keys, size_t n_key, const void* key_inde
 }
 
 }  // namespace
+
+// (msm_stages.cuh) the digit passes with the key / R boundary at N (every point a key, flags[p] its own: the coalesced equation's form
+// with no element), then the scan, the buckets and the windows over the wa windows in use
+int c25519_engine::batcheq_bucket_stages(const BatchEqScratch& s, size_t N, const BatchEqShape& sh, hipStream_t stream)
+{
+    const unsigned KB = (unsigned)(sh.wa * sh.buckets);
+    const unsigned pts = std::max(BE_BLOCK, 2 * sh.buckets);                      // (as batcheq_equation)
+    const dim3 dgrid(grid_for(N, (int)pts), (unsigned)sh.wa);
+    k_ed25519_keyeq_count<<<dgrid, BE_BLOCK, 0, stream>>>(s, N, 0, pts, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_scan<<<1, BE_SCAN_BLOCK, 0, stream>>>(s, KB);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_keyeq_scatter<<<dgrid, BE_BLOCK, 0, stream>>>(s, N, 0, pts, sh);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_buckets<<<grid_for(KB, ED_BLOCK), ED_BLOCK, 0, stream>>>(s, KB);
+    C25519_TRY(hipGetLastError());
+    k_ed25519_batcheq_windows<<<(unsigned)sh.wa, 64, 0, stream>>>(s, sh);
+    C25519_TRY(hipGetLastError());
+    return 0;
+}
 
 extern "C" {
 

@@ -2,7 +2,7 @@
 // between the kernels of a pass, the completion word, the shared inversion (k_batch_invert, its output encoders, launch_invert)
 // and the host-side helpers of the *_dev entry points (tables, argument checks, launch policy).
 //
-// The engine is THIRTEEN translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
+// The engine is FOURTEEN translation units, compiled in parallel by curve25519_amd/build.py and linked into one library:
 //   engine_x25519.hip      the Montgomery-ladder kernels; curve25519_dh_CreateSharedKey / _CalculatePublicKey (*_dev)
 //   engine_fixed_base.hip  the constant tables; key pairs, signatures, CalculatePublicKey_fast, blinding contexts (*_dev)
 //   engine_verify.hip      verification per element: the lattice path with its strict and ZIP-215 twins, the reference order (*_dev)
@@ -15,8 +15,9 @@
 //   engine_vrf.hip         ECVRF-EDWARDS25519-SHA512-ELL2 (RFC 9381): VRF_Prove, VRF_Verify, VRF_ProofToHash (*_dev)
 //   engine_oprf.hip        OPRF and VOPRF on ristretto255 (RFC 9497): OPRF_Blind, OPRF_Finalize, OPRF_BlindEvaluate, VOPRF_BlindEvaluate, VOPRF_VerifyProof (*_dev)
 //   engine_batch_eq.hip    ZIP-215 batch verification: one equation per call, a bucket-method multi-scalar multiplication (*_dev, *_batch)
+//   engine_msm.hip         multiscalar multiplication on both groups: MultiScalarMult, MultiScalarMult_vartime (*_dev)
 //   engine_api.hip         library state, unit-test hooks, the host-pointer *_batch forms, the reference's single-call prototypes
-// engine.hip includes all thirteen as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
+// engine.hip includes all fourteen as ONE translation unit: what the ISA tools, tests/test_resources.py and tools/build_variants.sh
 // compile (the same kernels; tests/test_build_units.py keeps the two lists and the directory in step).  Entry points are declared in
 // include/curve25519_amd.h, include/curve25519_dh.h and include/ed25519_signature.h (each cites the reference prototype it replaces).
 //

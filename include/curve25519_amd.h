@@ -55,7 +55,8 @@ int  c25519_amd_set_device(int device);                /* device used by this ho
  * contexts' rows; smaller calls gather the contexts' keys and run what curve25519_dh_CreateSharedKey_dev runs; default 2049;
  * 0 = always walk), BATCH_EQ_MIN / BATCH_EQ_WINDOW / BATCH_EQ_INDEXED_MIN (ed25519_VerifyBatch_zip215_*, see there), SCALARMULT_WINDOW
  * (ed25519_ScalarMult_* and ristretto255_ScalarMult_*: the window width of the variable-base walk, 2, 3 or 4; anything else: the built-in choice, 2, the fastest at 2^20),
- * SC_INVERT_K (ed25519_ScalarInvert_*: elements per inverting lane, 1, 2, 4, 8 or 16; anything else: the built-in choice by n, see there).
+ * SC_INVERT_K (ed25519_ScalarInvert_*: elements per inverting lane, 1, 2, 4, 8 or 16; anything else: the built-in choice by n, see there),
+ * MSM_BUCKET_MIN / MSM_WINDOW (*_MultiScalarMult_vartime_*, see there).
  * _get returns -1 for "built-in choice", -2 for an unknown name.
  * Environment only (read once): C25519_AMD_DONE_WORD=0 -- a host-pointer call of ONE element waits for the stream's event instead of
  * the completion word its last kernel stores behind the results (5 us later; same bytes); C25519_AMD_ZERO_COPY=0 -- calls of a
@@ -639,6 +640,68 @@ int ristretto255_VOPRF_VerifyProof_batch(int *req_ok /* m */, const unsigned cha
 int ristretto255_VOPRF_VerifyProof_dev(void *req_ok, const void *pkS, const void *blinded, const void *evaluated, const void *proof,
                                        const void *offsets, size_t m, size_t n, void *stream);
 size_t ristretto255_VOPRF_scratch_bytes(size_t m, size_t n);
+
+/* ---- multiscalar multiplication: Q = sum_i [s_i] P_i on edwards25519 and on ristretto255 ------------------------------------------
+ * What Pedersen and vector commitments, Bulletproofs-style verifiers, batched Schnorr / DLEQ / VRF checks and ElGamal are built on
+ * (curve25519-dalek: the traits MultiscalarMul and VartimeMultiscalarMul).  A call computes n_groups INDEPENDENT sums of m terms each:
+ * scalar and point are n_groups * m rows of 32 bytes, group g owns rows g * m .. g * m + m - 1; q is n_groups x 32 bytes, ok
+ * n_groups ints.  n_groups = 1 is dalek's call, m = 2 a batch of Pedersen commitments.  Every group of a call has the same m.
+ *   scalar   s_i is ALL 256 bits of the 32 bytes, little-endian, REDUCED MOD L -- how the ed25519_Scalar* calls read a scalar, NOT the
+ *            "low 255 bits" of the _noclamp calls: the two flavours below must give the same bytes on an Edwards point with a torsion
+ *            part ([s]P and [s mod L]P differ there), and the bucket method needs canonical scalars.
+ *   points   ed25519_*: decoded by the rule of ed25519_ScalarMult_* (ZIP-215: any 32 bytes with a square root), encoded canonically;
+ *            the neutral element is 01 00 .. 00.  ristretto255_*: RFC 9496 DECODE / ENCODE; the identity is 32 zero bytes.
+ *   verdict  ok[g] = 1 exactly when all m points of group g decode, and then q[g] is the sum; otherwise ok[g] = 0 and q[g] is 32 zero
+ *            bytes.  Other groups are not affected.  Every row of q and ok is written.
+ *   errors   n_groups = 0 returns 0 and does nothing.  m = 0, a null pointer, m > 2^26 (the bucket method's index entries hold a 32-bit
+ *            point index and a sign; c25519_multiscalar_max_m) or n_groups * m > 2^31 is an argument error (non-zero return, nothing
+ *            written).
+ *   _batch   stages the WHOLE call as one piece on one stream (a group is never cut across pipeline pieces, as with the VOPRF proof
+ *            calls) through a buffer of the calling thread that is zeroed before the call returns, and returns when it is done.
+ *   _dev     16-byte aligned device pointers and a stream; never synchronises, allocates nothing beyond one lease of
+ *            c25519_MultiScalarMult_scratch_bytes(m, n_groups, vartime) bytes of the calling thread's work scratch (under the current
+ *            tunables; 0 for sizes the calls refuse), and can be captured into a graph.
+ * SECRECY.  In ed25519_MultiScalarMult_* and ristretto255_MultiScalarMult_* the scalars are secret and the points public: no branch
+ * condition and no load or store address derives from a scalar -- not a table row, not a row fetch (tests/test_secret_taint_msm.py).
+ * The *_vartime_* calls are for PUBLIC inputs only: THEIR RUNNING TIME AND THEIR MEMORY ACCESSES DEPEND ON THE SCALARS (bucket
+ * addresses are the scalars' digits).  USE THEM ONLY WHERE EVERY SCALAR AND EVERY POINT IS PUBLIC (verification equations).
+ * How it runs.  Constant-time path (the plain calls at every size): one lane per row reduces the scalar, decodes the point and runs
+ * the group calls' variable-base walk (table in registers, rows selected by masks), leaving an extended point and a decode flag in
+ * scratch -- no encoding, no inversion; then passes in which one lane adds at most 64 consecutive points of a group by the complete
+ * addition (equal and opposite points need no case of their own) and ANDs their flags, until a group has one point: a group of 2^20
+ * rows is three short passes; then one lane per group: the Edwards encoding behind the shared inversion, the ristretto255 one in the
+ * lane.  Variable-time path (the _vartime calls with m >= MSM_BUCKET_MIN): the bucket method of ed25519_VerifyBatch_zip215_* per
+ * group, one group after the other over the same scratch -- packed rows of the points P_i themselves (nothing is negated), scalars
+ * reduced and biased, that call's count / scan / scatter / buckets / windows kernels unchanged, Horner over the windows and the
+ * encoding.  A _vartime call below MSM_BUCKET_MIN takes the constant-time path, which is a correct implementation of its contract.
+ * Tunables: MSM_BUCKET_MIN (smallest m of the bucket path for any number of groups; 0: never, 1: always; built-in: 2^10 for a call
+ * of ONE group, 2^18 for more) and MSM_WINDOW (the bucket path's window width, 7..13; anything else: the built-in choice, 10 below
+ * 2^14 points, 11 below 2^17, 12 from there).
+ * Measured (tools/msm_rate.py, profiles/msm_rate.txt; interleaved rounds, canonical random scalars, distinct points; beside each
+ * call the COMPOSED sequence a caller had before on the same inputs in the same process: ed25519_ScalarMult_noclamp_dev /
+ * ristretto255_ScalarMult_dev, then log2 m rounds of *_PointAdd_dev).  2^20 rows, Edwards / ristretto255, plain call against
+ * composed, ms: m = 2 11.59 / 12.01 against 12.33 / 13.48 (0.94 / 0.89 x); m = 64 11.76 / 11.85 against 13.43 / 14.99 (0.88 /
+ * 0.79 x); m = 4096 13.89 / 14.03 against 14.88 / 16.47; m = 2^16 13.95 / 14.00 against 15.60 / 17.46; m = 2^18 13.74 / 13.95
+ * against 15.78 / 17.80; m = 2^20 (one group) 13.82 / 13.57 against 16.00 / 17.87 (0.86 / 0.76 x): the plain call is not slower
+ * than the sequence at any shape (spreads 0.02-0.43 ms), 75-91 M rows/s.  The bucket path, one group, best width against the plain
+ * call (Edwards): 2^10 0.77 against 1.13 ms, 2^12 0.83 / 1.26, 2^14 0.97 / 1.30, 2^16 1.16 / 1.48, 2^17 1.44 / 2.31, 2^18 1.83 /
+ * 4.13, 2^19 2.58 / 7.34, 2^20 4.18 / 13.51 ms (0.31 x; as a call of its own 4.12 ms, 255 M rows/s; ristretto255 4.21 / 13.53): it
+ * wins from the smallest measured size by more than the rounds' spread (0.01-0.16 ms), and at 2^20 its 3.9 ns per point are the
+ * batch equation's 3.4 (7.17 ms for 2 x 2^20 points) plus the scalars' reduction.  Widths at 2^20: c = 12 4.12 ms, 13 4.73, 11
+ * 5.74, 10 14.2, 7 55.5.  Its groups run one after the other: 4 groups of 2^18 take 7.22 ms (plain 13.74), 16 groups of 2^16 19.6
+ * ms (plain 13.95: slower), 256 groups of 2^12 227 ms (plain 13.89) -- hence the larger built-in threshold for more than one group;
+ * shapes of more than 256 groups were not timed on that path. */
+#define c25519_multiscalar_max_m 67108864   /* 2^26 */
+int ed25519_MultiScalarMult_batch(unsigned char *q /* n_groups x 32 */, int *ok /* n_groups */, const unsigned char *scalar /* n_groups m x 32 */,
+                                  const unsigned char *point /* n_groups m x 32 */, size_t m, size_t n_groups);
+int ed25519_MultiScalarMult_dev(void *q, void *ok, const void *scalar, const void *point, size_t m, size_t n_groups, void *stream);
+int ed25519_MultiScalarMult_vartime_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t m, size_t n_groups);
+int ed25519_MultiScalarMult_vartime_dev(void *q, void *ok, const void *scalar, const void *point, size_t m, size_t n_groups, void *stream);
+int ristretto255_MultiScalarMult_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t m, size_t n_groups);
+int ristretto255_MultiScalarMult_dev(void *q, void *ok, const void *scalar, const void *point, size_t m, size_t n_groups, void *stream);
+int ristretto255_MultiScalarMult_vartime_batch(unsigned char *q, int *ok, const unsigned char *scalar, const unsigned char *point, size_t m, size_t n_groups);
+int ristretto255_MultiScalarMult_vartime_dev(void *q, void *ok, const void *scalar, const void *point, size_t m, size_t n_groups, void *stream);
+size_t c25519_MultiScalarMult_scratch_bytes(size_t m, size_t n_groups, int vartime);
 
 /* n x ed25519_VerifySignature (reference :67): full Init + Check per element, distinct keys.
  * Cost depends on the INPUT, which an untrusted sender controls: a key that does not decompress onto the curve sends its
